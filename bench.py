@@ -9,6 +9,7 @@ all-reduce + Adam.  value = residues/s over all ranks, inputs resident in HBM.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
   python bench.py --mode sample --n-res 256 --batch 1 --steps 1 --warmup 1        # full 500-step sampling
   python bench.py --mixed-n                                                         # BASELINE configs[3]
+  python bench.py --steps 10 --dump-outputs DIR     # + what the last timed step computed, DIR/<name>.npy (same inputs every run)
 
 Before the W warm-up steps the process runs FD_BENCH_PRIME (default 4) untimed priming steps (code-object loads, allocator
 growth) and then chunks of 4 more until two consecutive chunks agree within 1.5 % (GPU power state back from idle: at least 1.5 s, at most 4 s --
@@ -56,7 +57,12 @@ def parse():
     ap.add_argument("--cpu-sample-batch", type=int, default=4)
     ap.add_argument("--mixed-n", action="store_true",
                     help="BASELINE configs[3]: every step all ranks draw the same N in [100, 512], B = min(32, 5e5 // N^2)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -167,6 +173,36 @@ def _port_vs_reference():
         d = json.load(f)
     d["source"] = os.path.relpath(files[-1], ROOT)
     return d
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 20          # entries kept of an array larger than this: a fixed, seeded sample (<= 8 MB per file)
+
+
+def host_arrays(named):
+    """{name: tensor} -> {name: float32 / float64 numpy array} on the host; an array of more than DUMP_SAMPLE entries is
+    flattened and reduced to the entries at a fixed, seeded, sorted set of DUMP_SAMPLE indices (the same for every run)"""
+    import numpy as np
+    res = {}
+    for name, t in named.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.RandomState(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        res[name] = t.cpu().numpy()
+    return res
+
+
+def write_dump(dirname, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes > 64 MB"
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -449,6 +485,8 @@ def bench_sample(a, rank, world, dev, lib):
     barrier()
     dt = time.perf_counter() - t0
     assert torch.isfinite(out["rigids"]).all()
+    if a.dump_outputs and rank == 0:
+        write_dump(a.dump_outputs, host_arrays({k: v for k, v in out.items() if torch.is_tensor(v)}))
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -525,6 +563,7 @@ def main():
     # buffers: param.grad are views of ONE buffer (single RCCL all-reduce), the update is one launch
     opt = FlatAdam(model.parameters(), lr=1e-4, adjacent=model.flat_layout_groups())
     grads = opt
+    p_init = opt.flat_p.clone() if a.dump_outputs else None     # the state the last timed step of --dump-outputs starts from
     model.accumulate_into_grad = True      # backward kernels accumulate straight into the flat all-reduce buffer
     overlap = None
     if world > 1 and os.environ.get("FD_DP_OVERLAP", "0") != "0":
@@ -550,12 +589,13 @@ def main():
         sched = [(N, B)] * (a.warmup + a.steps)
         data = [make_batch(N, B, 100 + rank)] * (a.warmup + a.steps)
 
-    def step(i=0, self_cond=False):
+    def step(i=0, self_cond=False, keep=False):
+        """keep: return (network outputs, loss) -- only for the last timed step of --dump-outputs"""
         batch, gt37 = data[i % len(data)]
         if a.mode == "forward":
             with torch.no_grad():
-                model(batch)
-            return
+                out = model(batch)
+            return (out, None) if keep else None
         if self_cond:                                # train_se3_diffusion.py:519-522,535-537
             with torch.no_grad():
                 sc = model(batch)["rigids"][..., 4:]
@@ -569,6 +609,7 @@ def main():
         else:
             grads.all_reduce_mean()
         opt.step()
+        return (out, loss) if keep else None
 
     def barrier():
         torch.cuda.synchronize()
@@ -634,12 +675,29 @@ def main():
     marks[0].record()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        step(a.warmup + i)
+        keep = p_init is not None and i == a.steps - 1
+        if keep:
+            # --dump-outputs: the last timed step starts from the initial parameters and a fresh Adam state, so that its inputs are
+            # the same in every run (the steps before it -- their number set by the adaptive priming -- reduce gradients with
+            # atomics, and Adam carries that round-off into every parameter); one 70 MB device copy inside the timed region
+            opt.flat_p.copy_(p_init)
+            opt.exp_avg.zero_()
+            opt.exp_avg_sq.zero_()
+            opt.t = 0
+        last = step(a.warmup + i, keep=keep)
         marks[i + 1].record()
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
     dev_allocs = torch.cuda.memory_stats().get("num_device_alloc", 0) - dev_allocs0
+    if a.dump_outputs and rank == 0:
+        # copied to the host before any later step overwrites the parameters or the gradient buffer
+        out, loss = last
+        named = {k: v for k, v in out.items() if torch.is_tensor(v)}
+        if loss is not None:
+            named.update(loss=loss.reshape(1), params=opt.flat_p, grads=opt.flat_g)
+        write_dump(a.dump_outputs, host_arrays(named))
+    del last, p_init
     per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)]
     slowest_step = max(range(a.steps), key=lambda i: per_step[i])
     if os.environ.get("FD_BENCH_STEP_TRACE"):

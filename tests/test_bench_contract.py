@@ -45,6 +45,33 @@ def test_bench_line_single(hip_lib):
     assert cb["kind"] in ("port", "reference") and cb["value"] > 0 and cb["cores"] >= 1 and "sample" in cb
 
 
+def test_bench_dump_outputs(hip_lib, tmp_path):
+    """--dump-outputs DIR: what the last timed step computed (network outputs, loss, a fixed sample of the updated parameters and
+    of the gradient) as float .npy files.  The last timed step starts from the same state in every run, whatever the priming did,
+    so two runs with the same arguments dump the same arrays."""
+    import numpy as np
+
+    def run(name, prime):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--no-cpu-baseline", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, cwd=ROOT, env=dict(os.environ, FD_BENCH_PRIME=str(prime)), timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _line(r.stdout)
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        return {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+
+    a, b = run("a", 1), run("b", 5)
+    assert set(a) == set(b) >= {"psi", "rot_score", "trans_score", "rigids", "atom37", "loss", "params", "grads"}
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    # (atomics: the runs may differ in round-off, and an entry whose gradient is analytically zero takes an Adam step of +-lr on the
+    #  sign of that round-off -- one step of lr = 1e-4 from the same start)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.isfinite(a[k]).all() and a[k].shape == b[k].shape, k
+        err = float(np.abs(a[k] - b[k]).max())
+        bound = 2e-4 + 1e-6 if k == "params" else 1e-3 * float(np.abs(b[k]).max()) + 1e-6
+        assert err <= bound, (k, err, bound)
+
+
 def test_bench_two_ranks_on_one_gpu(hip_lib):
     """plain `python bench.py --gpus 2`: bench.py starts its two ranks itself (spawn_ranks -> torch.distributed.run); gloo and a
     forced device because RCCL refuses two ranks on one GPU -- on an 8-GPU node the same command runs over RCCL."""

@@ -190,7 +190,44 @@ __global__ __launch_bounds__(256) void bb_update_bwd_kernel(const float* __restr
 // f'  = sum_l (2l+1) w_l N/lo^2,  N = lo*dhi - hi*dlo
 // f'' = sum_l (2l+1) w_l [ hi (1/4 - a^2)/lo - 2 N dlo / lo^3 ]
 // sin/cos((l+1/2)w) by rotation recurrence, weights by ratio recurrence (both fp64).
+// below this omega the series runs in the Dirichlet-kernel form: sin((l+1/2)w)/sin(w/2) = 1 + 2 sum_{k=1..l} cos(kw), so
+// f' = sum_l (2l+1) w_l (-2 sum_{k<=l} k sin(kw)) and f'' likewise with -2 k^2 cos(kw).  The quotient-rule numerator N above
+// cancels to O(w^3) and loses ~1e-16 / (a w)^2 of f' relative: 8e-4 at the omega = 1e-6 of an identity relative rotation.
+constexpr double kDirichletOmega = 1e-2;
+
+__device__ __forceinline__ void igso3_series_small(double om, double sg, int L, double* f, double* df, double* d2f) {
+  const double so = sin(om), co = cos(om);
+  double s = 0.0, c = 1.0;                // sin, cos of k w at k = 0
+  const double q = exp(-sg * sg);
+  double w = 1.0, r = q;
+  double R0 = 1.0, R1 = 0.0, R2 = 0.0;    // the ratio at l and its first two derivatives
+  double F = 0.0, D = 0.0, D2 = 0.0;
+  for (int l = 0; l < L; ++l) {
+    if (l > 0) {
+      const double s2 = s * co + c * so;
+      c = c * co - s * so;
+      s = s2;
+      const double k = (double)l;
+      R0 += 2.0 * c;
+      R1 -= 2.0 * k * s;
+      R2 -= 2.0 * k * k * c;
+    }
+    const double cw = (double)(2 * l + 1) * w;
+    F += cw * R0;
+    D += cw * R1;
+    D2 += cw * R2;
+    w *= r;
+    r *= q;
+    if (w == 0.0) break;
+  }
+  *f = F; *df = D; *d2f = D2;
+}
+
 __device__ __forceinline__ void igso3_series(double om, double sg, int L, double* f, double* df, double* d2f) {
+  if (om < kDirichletOmega) {
+    igso3_series_small(om, sg, L, f, df, d2f);
+    return;
+  }
   const double lo = sin(0.5 * om), dlo = 0.5 * cos(0.5 * om);
   const double so = sin(om), co = cos(om);
   double s = lo, c = 2.0 * dlo;      // sin, cos of (l + 1/2) w at l = 0
@@ -256,20 +293,37 @@ struct HeadConst {
   int n_omega;
 };
 
-__device__ __forceinline__ void igso3_score(float omega, float tb, const double* __restrict__ sigma_grid, int ng,
+__device__ __forceinline__ void igso3_score(double omega, float tb, const double* __restrict__ sigma_grid, int ng,
                                             const HeadConst& hc, double* g, double* gp) {
   const int si = sigma_index((double)tb, sigma_grid, ng, hc.exp_max_sigma, hc.exp_min_sigma);
   if (hc.score_norms) {
-    *g = hc.score_norms[(long)si * hc.n_omega + omega_bucket((double)omega, hc.omega_grid, hc.n_omega)];
+    *g = hc.score_norms[(long)si * hc.n_omega + omega_bucket(omega, hc.omega_grid, hc.n_omega)];
     *gp = 0.0;
     return;
   }
   double f, df, d2f;
-  igso3_series((double)omega, sigma_grid[si], hc.L, &f, &df, &d2f);
+  igso3_series(omega, sigma_grid[si], hc.L, &f, &df, &d2f);
   const double fe = f + 1e-4;
   *g = df / fe;
   *gp = d2f / fe - df * df / (fe * fe);
 }
+
+// the relative rotation p = inv(qF) (x) q0 = conj(qF) (x) q0 / |qF|^2 (se3_diffuser.py:119-125) in the reference's fp32
+// arithmetic: where qF = q0 (a fixed residue) p is the identity up to the rounding of this product, and the reference's score
+// there is that rounding -- it is reproduced, not replaced by an fp64 zero.  What follows from p runs in fp64.
+__device__ __forceinline__ void rel_quat(const float* __restrict__ qf, const float* __restrict__ q0, double* pw, double* px,
+                                         double* py, double* pz) {
+  const float nn = qf[0] * qf[0] + qf[1] * qf[1] + qf[2] * qf[2] + qf[3] * qf[3];
+  const float cw = qf[0] / nn, cx = -qf[1] / nn, cy = -qf[2] / nn, cz = -qf[3] / nn;
+  *pw = cw * q0[0] - cx * q0[1] - cy * q0[2] - cz * q0[3];
+  *px = cw * q0[1] + cx * q0[0] + cy * q0[3] - cz * q0[2];
+  *py = cw * q0[2] - cx * q0[3] + cy * q0[0] + cz * q0[1];
+  *pz = cw * q0[3] + cx * q0[2] - cy * q0[1] + cz * q0[0];
+}
+
+// quat_to_rotvec's small-angle branch (data/utils.py:582-599), compared at the reference's precision: its fp32 angle against
+// the fp32 literal
+constexpr double kSmallAngle = (double)1e-3f;
 
 // thread per residue
 __global__ __launch_bounds__(128) void heads_fwd_kernel(
@@ -286,30 +340,29 @@ __global__ __launch_bounds__(128) void heads_fwd_kernel(
     const float tb = t[b];
     const float* q0 = rig0 + r * 7;
     const float* qf = quatF + r * 4;
-    // ---- rotation score: q0t = inv(qF) (x) q0
-    const float nn = qf[0] * qf[0] + qf[1] * qf[1] + qf[2] * qf[2] + qf[3] * qf[3];
-    const float cw = qf[0] / nn, cx = -qf[1] / nn, cy = -qf[2] / nn, cz = -qf[3] / nn;
-    float pw = cw * q0[0] - cx * q0[1] - cy * q0[2] - cz * q0[3];
-    float px = cw * q0[1] + cx * q0[0] + cy * q0[3] - cz * q0[2];
-    float py = cw * q0[2] - cx * q0[3] + cy * q0[0] + cz * q0[1];
-    float pz = cw * q0[3] + cx * q0[2] - cy * q0[1] + cz * q0[0];
-    if (pw < 0.f) { pw = -pw; px = -px; py = -py; pz = -pz; }
-    const float mm = sqrtf(px * px + py * py + pz * pz);
-    const float ang = 2.f * atan2f(mm, pw);
-    const float a2 = ang * ang;
-    const float sc = ang <= 1e-3f ? 2.f + a2 / 12.f + 7.f * a2 * a2 / 2880.f : ang / sinf(ang / 2.f + 1e-6f);
-    const float vx = sc * px, vy = sc * py, vz = sc * pz;
-    const float omega = sqrtf(vx * vx + vy * vy + vz * vz) + 1e-6f;
+    // ---- rotation score: q0t = inv(qF) (x) q0, then its rotation vector and omega in fp64 like the series they feed.  Near
+    // 180 degrees f'(omega) -> 0 and the score goes as (pi - omega): an fp32 omega (one ulp = 2.4e-7 there) would put
+    // 2.4e-7 / (pi - omega) into it, 2e-4 at pi - 1e-3.
+    double pw, px, py, pz;
+    rel_quat(qf, q0, &pw, &px, &py, &pz);
+    if (pw < 0.0) { pw = -pw; px = -px; py = -py; pz = -pz; }
+    const double mm = sqrt(px * px + py * py + pz * pz);
+    const double ang = 2.0 * atan2(mm, pw);
+    const double a2 = ang * ang;
+    const double sc = ang <= kSmallAngle ? 2.0 + a2 / 12.0 + 7.0 * a2 * a2 / 2880.0 : ang / sin(ang / 2.0 + 1e-6);
+    const double vx = sc * px, vy = sc * py, vz = sc * pz;
+    const double omega = sqrt(vx * vx + vy * vy + vz * vz) + 1e-6;
     double g, gp;
     igso3_score(omega, tb, sigma_grid, ng, hc, &g, &gp);
-    const double scal = g / (double)(omega + 1e-6f) * (double)m;
-    rot_score[r * 3 + 0] = scal * (double)vx;
-    rot_score[r * 3 + 1] = scal * (double)vy;
-    rot_score[r * 3 + 2] = scal * (double)vz;
-    // ---- translation score (fp32, reference arithmetic order)
+    const double scal = g / (omega + 1e-6) * (double)m;
+    rot_score[r * 3 + 0] = scal * vx;
+    rot_score[r * 3 + 1] = scal * vy;
+    rot_score[r * 3 + 2] = scal * vz;
+    // ---- translation score (fp32, reference arithmetic order).  The variance 1 - exp(-beta) is formed as -expm1(-beta):
+    // 1 - expf(-beta) cancels to ~6e-8 / beta relative at small t (3e-5 at t = 0.01, beta ~ 2e-3)
     const float cs = hc.coord_scale;
     const float beta = tb * hc.min_b + 0.5f * (tb * tb) * (hc.max_b - hc.min_b);
-    const float e1 = expf(-0.5f * beta), cv = 1.f - expf(-beta);
+    const float e1 = expf(-0.5f * beta), cv = -expm1f(-beta);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const float ta = transF[r * 3 + k] / cs;       // unscale_rigids (nm -> A)
@@ -389,65 +442,63 @@ __global__ __launch_bounds__(128) void heads_bwd_kernel(
     }
     if (d_trans_score) {
       const float beta = tb * hc.min_b + 0.5f * (tb * tb) * (hc.max_b - hc.min_b);
-      const float e1 = expf(-0.5f * beta), cv = 1.f - expf(-beta);
+      const float e1 = expf(-0.5f * beta), cv = -expm1f(-beta);     // (as in the forward)
 #pragma unroll
       for (int k = 0; k < 3; ++k) dtA[k] += d_trans_score[r * 3 + k] * m * (e1 * cs / cv);
     }
     if (d_rot) {
-      // recompute forward
-      const float nn = qf[0] * qf[0] + qf[1] * qf[1] + qf[2] * qf[2] + qf[3] * qf[3];
-      const float c0 = qf[0] / nn, c1 = -qf[1] / nn, c2 = -qf[2] / nn, c3 = -qf[3] / nn;
-      float pw = c0 * q0[0] - c1 * q0[1] - c2 * q0[2] - c3 * q0[3];
-      float px = c0 * q0[1] + c1 * q0[0] + c2 * q0[3] - c3 * q0[2];
-      float py = c0 * q0[2] - c1 * q0[3] + c2 * q0[0] + c3 * q0[1];
-      float pz = c0 * q0[3] + c1 * q0[2] - c2 * q0[1] + c3 * q0[0];
-      const float sgn = pw < 0.f ? -1.f : 1.f;
+      // recompute forward (as there)
+      double pw, px, py, pz;
+      rel_quat(qf, q0, &pw, &px, &py, &pz);
+      const double sgn = pw < 0.0 ? -1.0 : 1.0;
       pw *= sgn; px *= sgn; py *= sgn; pz *= sgn;
-      const float mm = sqrtf(px * px + py * py + pz * pz);
-      const float ang = 2.f * atan2f(mm, pw);
-      const float a2 = ang * ang;
-      float sc, dsc;
-      if (ang <= 1e-3f) {
-        sc = 2.f + a2 / 12.f + 7.f * a2 * a2 / 2880.f;
-        dsc = ang / 6.f + 7.f * a2 * ang / 720.f;
+      const double mm = sqrt(px * px + py * py + pz * pz);
+      const double ang = 2.0 * atan2(mm, pw);
+      const double a2 = ang * ang;
+      double sc, dsc;
+      if (ang <= kSmallAngle) {
+        sc = 2.0 + a2 / 12.0 + 7.0 * a2 * a2 / 2880.0;
+        dsc = ang / 6.0 + 7.0 * a2 * ang / 720.0;
       } else {
-        const float sh = sinf(ang / 2.f + 1e-6f), ch = cosf(ang / 2.f + 1e-6f);
+        const double sh = sin(ang / 2.0 + 1e-6), ch = cos(ang / 2.0 + 1e-6);
         sc = ang / sh;
-        dsc = 1.f / sh - ang * ch * 0.5f / (sh * sh);
+        dsc = 1.0 / sh - ang * ch * 0.5 / (sh * sh);
       }
-      const float vx = sc * px, vy = sc * py, vz = sc * pz;
-      const float vn = sqrtf(vx * vx + vy * vy + vz * vz);
-      const float omega = vn + 1e-6f;
+      const double vx = sc * px, vy = sc * py, vz = sc * pz;
+      const double vn = sqrt(vx * vx + vy * vy + vz * vz);
+      const double omega = vn + 1e-6;
       double g, gp;
       igso3_score(omega, tb, sigma_grid, ng, hc, &g, &gp);
-      const double den = (double)(omega + 1e-6f);
+      const double den = omega + 1e-6;
       const double gx = d_rot[r * 3] * (double)m, gy = d_rot[r * 3 + 1] * (double)m, gz = d_rot[r * 3 + 2] * (double)m;
       // s = g(w) v / den ; w = |v| + eps ; den = w + eps
       const double vdot = gx * vx + gy * vy + gz * vz;
-      const double radial = vn > 0.f ? vdot * (gp / den - g / (den * den)) / (double)vn : 0.0;
-      const float dvx = (float)(g / den * gx + radial * vx);
-      const float dvy = (float)(g / den * gy + radial * vy);
-      const float dvz = (float)(g / den * gz + radial * vz);
+      const double radial = vn > 0.0 ? vdot * (gp / den - g / (den * den)) / vn : 0.0;
+      const double dvx = g / den * gx + radial * vx;
+      const double dvy = g / den * gy + radial * vy;
+      const double dvz = g / den * gz + radial * vz;
       // v = sc(ang) * u ; ang = 2 atan2(|u|, w)
-      const float dvu = dvx * px + dvy * py + dvz * pz;
-      const float r2 = mm * mm + pw * pw;
-      const float dang_dm = 2.f * pw / r2, dang_dw = -2.f * mm / r2;
-      const float km = mm > 0.f ? dvu * dsc * dang_dm / mm : 0.f;
-      float dpx = sc * dvx + km * px, dpy = sc * dvy + km * py, dpz = sc * dvz + km * pz;
-      float dpw = dvu * dsc * dang_dw;
+      const double dvu = dvx * px + dvy * py + dvz * pz;
+      const double r2 = mm * mm + pw * pw;
+      const double dang_dm = 2.0 * pw / r2, dang_dw = -2.0 * mm / r2;
+      const double km = mm > 0.0 ? dvu * dsc * dang_dm / mm : 0.0;
+      double dpx = sc * dvx + km * px, dpy = sc * dvy + km * py, dpz = sc * dvz + km * pz;
+      double dpw = dvu * dsc * dang_dw;
       dpw *= sgn; dpx *= sgn; dpy *= sgn; dpz *= sgn;
       // p = c (x) q0  =>  dc = dp (x) conj(q0)
-      const float e0 = q0[0], e1 = -q0[1], e2 = -q0[2], e3 = -q0[3];
-      const float dc0 = dpw * e0 - dpx * e1 - dpy * e2 - dpz * e3;
-      const float dc1 = dpw * e1 + dpx * e0 + dpy * e3 - dpz * e2;
-      const float dc2 = dpw * e2 - dpx * e3 + dpy * e0 + dpz * e1;
-      const float dc3 = dpw * e3 + dpx * e2 - dpy * e1 + dpz * e0;
+      const double e0 = q0[0], e1 = -(double)q0[1], e2 = -(double)q0[2], e3 = -(double)q0[3];
+      const double dc0 = dpw * e0 - dpx * e1 - dpy * e2 - dpz * e3;
+      const double dc1 = dpw * e1 + dpx * e0 + dpy * e3 - dpz * e2;
+      const double dc2 = dpw * e2 - dpx * e3 + dpy * e0 + dpz * e1;
+      const double dc3 = dpw * e3 + dpx * e2 - dpy * e1 + dpz * e0;
       // c = conj(qF) / nn
-      const float dnn = -(dc0 * qf[0] - dc1 * qf[1] - dc2 * qf[2] - dc3 * qf[3]) / (nn * nn);
-      dq[0] += dc0 / nn + 2.f * qf[0] * dnn;
-      dq[1] += -dc1 / nn + 2.f * qf[1] * dnn;
-      dq[2] += -dc2 / nn + 2.f * qf[2] * dnn;
-      dq[3] += -dc3 / nn + 2.f * qf[3] * dnn;
+      const double f0 = qf[0], f1 = qf[1], f2 = qf[2], f3 = qf[3];
+      const double nn = f0 * f0 + f1 * f1 + f2 * f2 + f3 * f3;
+      const double dnn = -(dc0 * f0 - dc1 * f1 - dc2 * f2 - dc3 * f3) / (nn * nn);
+      dq[0] += (float)(dc0 / nn + 2.0 * f0 * dnn);
+      dq[1] += (float)(-dc1 / nn + 2.0 * f1 * dnn);
+      dq[2] += (float)(-dc2 / nn + 2.0 * f2 * dnn);
+      dq[3] += (float)(-dc3 / nn + 2.0 * f3 * dnn);
     }
     float dps = 0.f, dpc = 0.f;
     if (d_psi) { dps += d_psi[r * 2]; dpc += d_psi[r * 2 + 1]; }

@@ -1,7 +1,8 @@
 """fd_ipa_flash_fwd -- IPA attention of a trunk block in one launch (model/ipa_pytorch.py:380-457: logits, softmax, o, o_pt,
 |o_pt|, o_pair) -- against (1) the launch sequence it replaces (q k^T GEMM -> fd_ipa_attn_fwd -> a v / a v_pts GEMMs ->
-fd_ipa_opt_fwd, themselves oracle-tested) and (2) a float64 restatement of the reference's arithmetic on the same inputs.
-Tolerances are relative to each output group's maximum and <= 10 x what the kernel achieves (recorded by parity_log)."""
+fd_ipa_opt_fwd; the point and o_pt kernels have their own float64 test in test_frames.py) and (2) a float64 restatement of
+the reference's arithmetic on the same inputs.  Tolerances are relative to each output group's maximum and <= 10 x what the
+kernel achieves (recorded by parity_log)."""
 import math
 
 import pytest

@@ -6,6 +6,7 @@ config/base.yaml full depth (4 IPA blocks), one batch of B=30 backbones of N=128
 all-reduce + Adam.  value = residues/s over all ranks, inputs resident in HBM.
 
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full     # + every other measurement of the line (below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
   python bench.py --mode sample --n-res 256 --batch 1 --steps 1 --warmup 1        # full 500-step sampling
   python bench.py --mixed-n                                                         # BASELINE configs[3]
@@ -16,10 +17,14 @@ growth) and then chunks of 4 more until two consecutive chunks agree within 1.5 
 FD_BENCH_PRIME_MIN_S / FD_BENCH_PRIME_MAX_S); the timed region is exactly K steps between two barriers.
 
 One JSON line on stdout (rank 0):
-  * value / ms_per_step: the training step (the first half of BASELINE.json's metric);
+  * value / ms_per_step: the training step (the first half of BASELINE.json's metric).
+A plain run ends there (set-up, priming, warm-up, the timed steps, --dump-outputs, the line).  With --full the line also carries
+what takes runs of its own after the timed region:
   * config.sampling: the second half -- backbones/s of 500-step reverse diffusion at N = 128 / 256 / 512, from bounded
     device-resident runs (--sample-steps diffusion steps each, scaled to 501 network forwards; rank 0 at N = 1 GPU only);
+  * config.mixed_n: BASELINE configs[3] (12 steps of the mixed-length schedule; rank 0 at N = 1 GPU only);
   * config.self_conditioning_50pct: the step with the reference's 50 % extra no-grad forward (train_se3_diffusion.py:535-537);
+  * config.ms_per_step_exact_f32_gemms: the step with every GEMM on the bitwise-fp32 MFMA chain;
   * roofline: the dominant kernel (largest share of the serialised step among fd_gemm's tiles and the fused
     edge-transition kernel), timed with HIP events on its own stream in three steps right after the timed region;
   * cpu_baseline: the unmodified reference when FD_REFERENCE_ROOT (default /root/reference) exists, else the oracle (CPU port),
@@ -50,8 +55,11 @@ def parse():
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--mode", default="train", choices=["train", "forward", "sample"])
     ap.add_argument("--num-t", type=int, default=500, help="reverse-diffusion steps per backbone (sample mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sampling", action="store_true", help="skip the bounded sampling runs of the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: sampling, mixed lengths, "
+                         "self-conditioning, exact-fp32 GEMMs, roofline, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-sampling", action="store_true", help="--full without the sampling and mixed-length runs")
     ap.add_argument("--sample-steps", type=int, default=50, help="diffusion steps of each bounded sampling run")
     ap.add_argument("--no-graph", action="store_true", help="sample mode: eager launches instead of one hipGraph per step")
     ap.add_argument("--cpu-sample-batch", type=int, default=4)
@@ -470,15 +478,17 @@ def bench_sample(a, rank, world, dev, lib):
     for _ in range(a.warmup):
         step()
     barrier()
-    # per-kernel timing of the dominant kernel: HIP events around every profiled launch of three network forwards
-    # on the stream they run on (the timed region below replays captured graphs, where events cannot be read back)
+    # per-kernel timing of the dominant kernel (--full): HIP events around every profiled launch of three network forwards
+    # on the stream they run on (the timed region below replays captured graphs, where events cannot be read back).  The
+    # input is drawn in every run: the timed steps draw from `gen` after it, so their backbones do not depend on --full.
     pf = sampler.init_feats(diff, B, N, dev, generator=gen)
-    lib.gemm_profile = []
-    with torch.no_grad():
-        for _ in range(3):
-            model(pf)
-    torch.cuda.synchronize()
-    prof, lib.gemm_profile = lib.gemm_profile, None
+    if a.full:
+        lib.gemm_profile = []
+        with torch.no_grad():
+            for _ in range(3):
+                model(pf)
+        torch.cuda.synchronize()
+        prof, lib.gemm_profile = lib.gemm_profile, None
     t0 = time.perf_counter()
     for _ in range(a.steps):
         out = step()
@@ -493,9 +503,6 @@ def bench_sample(a, rank, world, dev, lib):
     dt = float(tmax.item())
     if rank != 0:
         return
-    tile, use_f, use_t, _n, tot_f, tot_t, _shape, _by = dominant_kernel(prof)
-    kname, peak = _KERNELS[tile]
-    achieved = use_f / max(use_t, 1e-9) / 1e12
     res = {
         "metric": f"backbones/sec {a.num_t}-step sampling @ N={N}", "value": round(world * B * a.steps / dt, 4),
         "unit": "backbones/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -505,11 +512,15 @@ def bench_sample(a, rank, world, dev, lib):
                                f"batch of {B} backbones x N={N}, config/base.yaml ScoreNetwork ({a.blocks} blocks), device-resident loop",
                    "parallelism": f"replicas x{world}", "ms_per_diffusion_step": round(dt / a.steps / a.num_t * 1e3, 3),
                    "igso3_table_build_s": round(t_tab, 2), "arithmetic": ARITH},
-        "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": None, "kernel": kname,
-                     "measured_on": "3 eager network forwards (HIP events per profiled launch)",
-                     "step_model_tflops": round(tot_f / 3 * (a.num_t + 1) * a.steps / dt / 1e12, 2)},
     }
+    if a.full:
+        tile, use_f, use_t, _n, tot_f, tot_t, _shape, _by = dominant_kernel(prof)
+        kname, peak = _KERNELS[tile]
+        achieved = use_f / max(use_t, 1e-9) / 1e12
+        res["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                           "frac": round(achieved / peak, 4), "traffic": None, "kernel": kname,
+                           "measured_on": "3 eager network forwards (HIP events per profiled launch)",
+                           "step_model_tflops": round(tot_f / 3 * (a.num_t + 1) * a.steps / dt / 1e12, 2)}
     print(json.dumps(res), flush=True)
 
 
@@ -722,9 +733,11 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
     residues = sum(n * b for n, b in sched[a.warmup:])
+    # With --full, runs of their own follow the timed region (the module docstring lists what they measure); a plain run goes
+    # straight to the line.
     # the reference's training step with its 50 % self-conditioning forward (every other step here), same shapes
     sc_ms = None
-    if a.mode == "train" and not a.mixed_n and not os.environ.get("FD_BENCH_PROFILE"):   # (profiler runs: the plain step only)
+    if a.full and a.mode == "train" and not a.mixed_n and not os.environ.get("FD_BENCH_PROFILE"):   # (profiler runs: the plain step only)
         k = max(2, a.steps - a.steps % 2)
         barrier()
         t0 = time.perf_counter()
@@ -737,18 +750,19 @@ def main():
     # the GPU with.  The roofline of the dominant kernel is taken from three more steps right after it, same shapes and
     # data, with that side stream switched off (launches serialised) and events around every profiled launch on the
     # stream it runs on.
-    from se3_diffusion_amd import ops as fops
-    side_was = fops.set_grad_stream(False)
-    lib.gemm_profile = []
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    prof, lib.gemm_profile = lib.gemm_profile, None
-    fops.set_grad_stream(side_was)
+    if a.full:
+        from se3_diffusion_amd import ops as fops
+        side_was = fops.set_grad_stream(False)
+        lib.gemm_profile = []
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        prof, lib.gemm_profile = lib.gemm_profile, None
+        fops.set_grad_stream(side_was)
     # the same step with every GEMM on the exact fp32 MFMA (bitwise fmaf-chain products: FD_GEMM_EXACT_F32=1; the fused
     # edge-transition kernel off), so the line carries both arithmetic choices; not part of `value`
     exact_ms = None
-    if not os.environ.get("FD_BENCH_PROFILE") and not a.mixed_n:   # (rocprofv3 runs: keep the trace to the shipped arithmetic)
+    if a.full and not os.environ.get("FD_BENCH_PROFILE") and not a.mixed_n:   # (rocprofv3 runs: keep the trace to the shipped arithmetic)
         was_exact = lib.set_exact_f32(True)
         step()
         barrier()
@@ -761,21 +775,7 @@ def main():
 
     if rank != 0:
         return
-    if os.environ.get("FD_BENCH_GEMM_DETAIL"):
-        shapes = {}
-        for p in prof:
-            s = shapes.setdefault((p[0], p[1], p[2]) + p[6], [0.0, 0.0, 0])
-            s[0] += p[3]; s[1] += p[4].elapsed_time(p[5]) * 1e-3; s[2] += 1
-        rows = sorted(shapes.items(), key=lambda kv: -kv[1][1])
-        sys.stderr.write("tile akc bkc (M,N,K,batch,gate,beta,pair,ksplit)  calls/step  ms/step  TF/s\n")
-        for k, v in rows[:80]:
-            sys.stderr.write(f"{k}  {v[2] / 3:.1f}  {v[1] / 3 * 1e3:.3f}  {v[0] / v[1] / 1e12:.1f}\n")
-    tile, dflops, dtime, dn, all_flops, tot_t, dshape, by_tile = dominant_kernel(prof)
-    kname, peak = _KERNELS[tile]
-    achieved = dflops / dtime / 1e12
-    nprof = 3
     ms = dt / a.steps * 1e3
-    traffic = pmc_traffic(tile, dshape[0])
     workload = (f"config/base.yaml ScoreNetwork ({a.blocks} IPA blocks, 17.4M params), per-GPU batch "
                 + (f"B={B} x N={N} residues" if not a.mixed_n else
                    "of same-length backbones, N ~ U{100..512} per step shared by all ranks, B = min(32, 5e5 // N^2) "
@@ -802,34 +802,50 @@ def main():
                                               "the slow one of every run (~ +2.5 ms); device_allocations = hipMalloc calls of torch's "
                                               "caching allocator inside the timed region (0 = every buffer came out of the cache)"},
                    "scaling_curve": "not measured by this line (one N per invocation; the driver composes 1/2/4/8)",
-                   "ms_per_step_exact_f32_gemms": None if exact_ms is None else round(exact_ms, 3),
-                   "self_conditioning_50pct": None if sc_ms is None else {
-                       "ms_per_step": round(sc_ms, 3), "residues_per_s": round(world * B * N / sc_ms * 1e3, 1),
-                       "note": "every other step runs the reference's extra no-grad forward (train_se3_diffusion.py:535-537)"},
                    "arithmetic": ARITH},
-        "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4),
-                     "traffic": None if traffic is None else traffic["bytes_per_launch"], "kernel": kname,
-                     "vs_fp32_mfma_peak": round(achieved / 157.3, 4),
-                     "frac_of_sustained_peak": None if peak < 400 else round(achieved / SUSTAINED_SPLIT_PEAK, 4),
-                     "sustained_peak": None if peak < 400 else SUSTAINED_SPLIT_PEAK,
-                     "sustained_peak_note": "v_mfma_f32_32x32x16_bf16 on register operands, every SIMD busy, random data: 1.76 of the "
-                                            "nominal 2.5 PFLOP/s (power-limited; tools/probes/mfma_peak.hip), / 6 products",
-                     "traffic_detail": traffic,
-                     "traffic_note": None if traffic is None else
-                     "HBM bytes per launch, launch-weighted over the variants of this kernel the step runs (rocprofv3 --pmc FETCH_SIZE "
-                     "/ WRITE_SIZE in separate passes, calibrated on known 1 GiB transfers: tools/pmc_roofline.sh)",
-                     "measured_on": "3 steps right after the timed region with the gradient side stream off "
-                                    "(HIP events per profiled launch on its stream)",
-                     "launches_per_step": dn // nprof,
-                     "avg_launch_us": round(dtime / max(1, dn) * 1e6, 2),
-                     "algorithmic_flops_per_launch": round(dflops / max(1, dn), 1),
-                     "serialised_ms_per_step_by_kernel_class": {str(k): round(v / nprof, 3) for k, v in by_tile.items()},
-                     "serialised_gemm_ms_per_step": round(tot_t / nprof * 1e3, 3),
-                     "all_gemm_tflops": round(all_flops / max(tot_t, 1e-9) / 1e12, 2),
-                     "step_model_tflops": round(all_flops / nprof / (dt / a.steps) / 1e12, 2)},
     }
-    if world == 1 and a.mode == "train" and not a.no_sampling and not a.mixed_n and not os.environ.get("FD_BENCH_PROFILE"):
+    if a.full:
+        if os.environ.get("FD_BENCH_GEMM_DETAIL"):
+            shapes = {}
+            for p in prof:
+                s = shapes.setdefault((p[0], p[1], p[2]) + p[6], [0.0, 0.0, 0])
+                s[0] += p[3]; s[1] += p[4].elapsed_time(p[5]) * 1e-3; s[2] += 1
+            rows = sorted(shapes.items(), key=lambda kv: -kv[1][1])
+            sys.stderr.write("tile akc bkc (M,N,K,batch,gate,beta,pair,ksplit)  calls/step  ms/step  TF/s\n")
+            for k, v in rows[:80]:
+                sys.stderr.write(f"{k}  {v[2] / 3:.1f}  {v[1] / 3 * 1e3:.3f}  {v[0] / v[1] / 1e12:.1f}\n")
+        tile, dflops, dtime, dn, all_flops, tot_t, dshape, by_tile = dominant_kernel(prof)
+        kname, peak = _KERNELS[tile]
+        achieved = dflops / dtime / 1e12
+        nprof = 3
+        traffic = pmc_traffic(tile, dshape[0])
+        res["config"]["ms_per_step_exact_f32_gemms"] = None if exact_ms is None else round(exact_ms, 3)
+        res["config"]["self_conditioning_50pct"] = None if sc_ms is None else {
+            "ms_per_step": round(sc_ms, 3), "residues_per_s": round(world * B * N / sc_ms * 1e3, 1),
+            "note": "every other step runs the reference's extra no-grad forward (train_se3_diffusion.py:535-537)"}
+        res["roofline"] = {
+            "bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+            "frac": round(achieved / peak, 4),
+            "traffic": None if traffic is None else traffic["bytes_per_launch"], "kernel": kname,
+            "vs_fp32_mfma_peak": round(achieved / 157.3, 4),
+            "frac_of_sustained_peak": None if peak < 400 else round(achieved / SUSTAINED_SPLIT_PEAK, 4),
+            "sustained_peak": None if peak < 400 else SUSTAINED_SPLIT_PEAK,
+            "sustained_peak_note": "v_mfma_f32_32x32x16_bf16 on register operands, every SIMD busy, random data: 1.76 of the "
+                                   "nominal 2.5 PFLOP/s (power-limited; tools/probes/mfma_peak.hip), / 6 products",
+            "traffic_detail": traffic,
+            "traffic_note": None if traffic is None else
+            "HBM bytes per launch, launch-weighted over the variants of this kernel the step runs (rocprofv3 --pmc FETCH_SIZE "
+            "/ WRITE_SIZE in separate passes, calibrated on known 1 GiB transfers: tools/pmc_roofline.sh)",
+            "measured_on": "3 steps right after the timed region with the gradient side stream off "
+                           "(HIP events per profiled launch on its stream)",
+            "launches_per_step": dn // nprof,
+            "avg_launch_us": round(dtime / max(1, dn) * 1e6, 2),
+            "algorithmic_flops_per_launch": round(dflops / max(1, dn), 1),
+            "serialised_ms_per_step_by_kernel_class": {str(k): round(v / nprof, 3) for k, v in by_tile.items()},
+            "serialised_gemm_ms_per_step": round(tot_t / nprof * 1e3, 3),
+            "all_gemm_tflops": round(all_flops / max(tot_t, 1e-9) / 1e12, 2),
+            "step_model_tflops": round(all_flops / nprof / (dt / a.steps) / 1e12, 2)}
+    if a.full and world == 1 and a.mode == "train" and not a.no_sampling and not a.mixed_n and not os.environ.get("FD_BENCH_PROFILE"):
         # BASELINE configs[3] on this GPU inside the same driver-timed command: 12 steps of the mixed-length schedule
         # (dist.mixed_length_schedule: N ~ U{100..512}, B = min(32, 5e5 // N^2)); every length runs once untimed first (new
         # lengths = first use of kernel variants + allocator growth)
@@ -853,7 +869,7 @@ def main():
                         "B = min(32, 5e5 // N^2); `python bench.py --mixed-n` is the same measurement as its own line"}
         except Exception as e:  # noqa: BLE001 -- must not lose the training measurement
             res["config"]["mixed_n"] = {"error": repr(e)}
-    if world == 1 and a.mode == "train" and not a.no_sampling and not a.mixed_n:
+    if a.full and world == 1 and a.mode == "train" and not a.no_sampling and not a.mixed_n:
         try:
             data.clear()
             torch.cuda.empty_cache()
@@ -864,7 +880,7 @@ def main():
                      f"steps scaled to 501 forwards")
         except Exception as e:  # noqa: BLE001 -- must not lose the training measurement
             res["config"]["sampling"] = {"error": repr(e)}
-    if not a.no_cpu_baseline and world == 1 and not a.mixed_n:
+    if a.full and not a.no_cpu_baseline and world == 1 and not a.mixed_n:
         try:
             res["cpu_baseline"] = cpu_baseline(N, a.blocks, a.cpu_sample_batch)
         except Exception as e:  # noqa: BLE001 -- the baseline must not lose the GPU measurement

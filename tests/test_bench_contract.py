@@ -1,7 +1,7 @@
-"""bench.py's output contract (one JSON line with the driver's fields + `roofline` + `cpu_baseline`) on a small configuration,
-and a rehearsal of its multi-rank path: `python bench.py --gpus 2` starting its own two ranks on ONE GPU (FD_DIST_BACKEND=gloo,
-FD_FORCE_DEVICE=0 -- RCCL refuses two ranks on a device), i.e. the per-rank data, parameter broadcast, flat all-reduce,
-barrier-bracketed timing and max-over-ranks code that `--gpus N` runs on an 8-GPU node."""
+"""bench.py's output contract (one JSON line with the driver's fields; with --full also `roofline` + `cpu_baseline`) on a small
+configuration, and a rehearsal of its multi-rank path: `python bench.py --gpus 2` starting its own two ranks on ONE GPU
+(FD_DIST_BACKEND=gloo, FD_FORCE_DEVICE=0 -- RCCL refuses two ranks on a device), i.e. the per-rank data, parameter broadcast, flat
+all-reduce, barrier-bracketed timing and max-over-ranks code that `--gpus N` runs on an 8-GPU node."""
 import json
 import os
 import socket
@@ -13,6 +13,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 SMALL = ["--n-res", "32", "--batch", "2", "--blocks", "1", "--steps", "2", "--warmup", "1", "--no-sampling"]
+# what only --full measures: keys of the line and of its `config`
+FULL_ONLY = {"roofline", "cpu_baseline"}
+FULL_ONLY_CONFIG = {"sampling", "mixed_n", "self_conditioning_50pct", "ms_per_step_exact_f32_gemms"}
 
 
 def _line(out):
@@ -21,14 +24,18 @@ def _line(out):
     return json.loads(lines[0])
 
 
-def _check(d, n):
+def _check(d, n, full=True):
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-              "dtype", "data", "config", "roofline"):
+              "dtype", "data", "config"):
         assert k in d, k
     assert d["n_gpus"] == n and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "residues/s" and d["scaling"] == "weak"
     assert d["value"] > 0 and abs(d["value"] - n * 2 * 32 / d["ms_per_step"] * 1e3) < 0.02 * d["value"]
-    r = d["roofline"]
-    assert r["bound"] in ("mfma", "hbm") and 0 < r["frac"] < 1 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    if full:
+        r = d["roofline"]
+        assert r["bound"] in ("mfma", "hbm") and 0 < r["frac"] < 1 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
+    else:
+        assert not FULL_ONLY & set(d) and not FULL_ONLY_CONFIG & set(d["config"]), (sorted(d), sorted(d["config"]))
     assert "workload" in d["config"] and "model" not in d["config"]
     sp = d["config"]["step_ms_spread"]
     assert sp["min"] <= sp["median"] <= sp["max"] and 0 <= sp["slowest_step"] < d["steps"] and sp["device_allocations_in_timed_region"] >= 0
@@ -36,13 +43,25 @@ def _check(d, n):
 
 def test_bench_line_single(hip_lib):
     env = dict(os.environ, FD_BENCH_PRIME="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--cpu-sample-batch", "1"], capture_output=True,
-                       text=True, cwd=ROOT, env=env, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--full", "--cpu-sample-batch", "1"],
+                       capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
     _check(d, 1)
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("port", "reference") and cb["value"] > 0 and cb["cores"] >= 1 and "sample" in cb
+
+
+@pytest.mark.parametrize("ranks", [1, 2])
+def test_bench_plain_line(hip_lib, ranks):
+    """without --full the line carries the headline figure and nothing that takes runs of its own after the timed steps (two
+    ranks: gloo on one GPU, as test_bench_two_ranks_on_one_gpu)"""
+    env = dict(os.environ, FD_BENCH_PRIME="1", FD_DIST_BACKEND="gloo", FD_FORCE_DEVICE="0")
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), *SMALL],
+                       capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    _check(_line(r.stdout), ranks, full=False)
 
 
 def test_bench_dump_outputs(hip_lib, tmp_path):
@@ -77,7 +96,7 @@ def test_bench_two_ranks_on_one_gpu(hip_lib):
     forced device because RCCL refuses two ranks on one GPU -- on an 8-GPU node the same command runs over RCCL."""
     env = dict(os.environ, FD_BENCH_PRIME="1", FD_DIST_BACKEND="gloo", FD_FORCE_DEVICE="0")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--full"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _line(r.stdout)
@@ -94,7 +113,7 @@ def test_bench_under_torchrun(hip_lib):
     s.close()
     env = dict(os.environ, FD_BENCH_PRIME="1", FD_DIST_BACKEND="gloo", FD_FORCE_DEVICE="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL],
+                        "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--full"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     _check(_line(r.stdout), 2)
@@ -114,7 +133,7 @@ def test_bench_two_ranks_over_rccl(hip_lib, overlap):
     env = dict(os.environ, FD_BENCH_PRIME="1", HSA_ENABLE_IPC_MODE_LEGACY="0", FD_DP_OVERLAP=overlap)
     for k in ("WORLD_SIZE", "FD_DIST_BACKEND", "FD_FORCE_DEVICE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", *SMALL, "--full"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     d = _line(r.stdout)
@@ -133,7 +152,7 @@ def test_bench_takes_world_size_from_the_launcher(hip_lib):
     s.close()
     env = dict(os.environ, FD_BENCH_PRIME="1", FD_DIST_BACKEND="gloo", FD_FORCE_DEVICE="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), *SMALL],
+                        "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), *SMALL, "--full"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     assert "measuring 2 ranks" in r.stderr

@@ -6,7 +6,7 @@ timeout 1500 python -m pytest tests -m gpu -q > $O/gputest.log 2>&1; echo "pytes
 tail -5 $O/gputest.log
 grep "\[parity\]" $O/gputest.log | tail -12
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -3 $O/smoke.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/final/bench_default.json').read())

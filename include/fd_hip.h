@@ -569,6 +569,20 @@ int fd_se3_reverse_step_net(const float* rig_t, const double* rot_score, const f
  * rotation block then translation block per step, refilled by the caller every K steps); *counter = idx + 1.  One block. */
 int fd_sample_advance(int* counter, const float* all_t, const double* all_tp, const double* z_all, int K, long nz, float* t_out,
                       int B, double* tparams, double* z_out, void* stream);
+/* The trajectory bookkeeping of Experiment.inference_fn(aux_traj=True) (experiments/train_se3_diffusion.py:782-803: four
+ * du.move_to_np copies and two compute_backbone calls per step, flipped at :805-812) as ONE launch per diffusion step into
+ * preallocated device buffers.  Rows R = B*N, contiguous fp32.  step = (slot_ptr ? *slot_ptr : 0) + slot_offset (slot_ptr: a
+ * device int the kernel only reads, e.g. the counter of fd_sample_advance with slot_offset = -1); the slice is written at the
+ * FLIPPED index T-1-step of
+ *   rigid_traj [T+1,R,7]  rigids_t (:782-784; index T is the starting frames, written by the caller)
+ *   bb_t       [T,R,5,3]  N, CA, C, CB, O of compute_backbone(rigids_t, psi) (:801-803)
+ *   bb_0       [T,R,5,3]  the same atoms of compute_backbone(rigid_pred, psi) (:794-799)
+ *   trans_0    [T,R,3]    (1-fixed_mask)*res_mask * rigid_pred[4:7] + fixed_mask*res_mask * rigids_t[4:7] (:787-790)
+ * aux = 0 (aux_traj=False): bb_t only; rigid_pred, the masks and the other three buffers may be NULL.  A step outside [0,T) is an
+ * argument error when slot_ptr is NULL and a skipped write otherwise. */
+int fd_sample_record(const float* rigids_t, const float* rigid_pred, const float* psi, const float* fixed_mask,
+                     const float* res_mask, const FdHeadConst* c, const int* slot_ptr, int slot_offset, int T, long R, int aux,
+                     float* rigid_traj, float* bb_t, float* bb_0, float* trans_0, void* stream);
 
 /* ---- training loss (the step next to the hot path): experiments/train_se3_diffusion.py:524-693 ----
  * Experiment.loss_fn, both rotation branches: translation score / x0 loss, rotation axis + angle (or joint MSE) loss,

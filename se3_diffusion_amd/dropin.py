@@ -13,6 +13,12 @@ experiment utils, configs) keeps working as is:
     from experiments import train_se3_diffusion       # now trains through libfd_hip.so
 
 or, from a shell:  python -m se3_diffusion_amd.dropin /path/to/se3_diffusion experiments/train_se3_diffusion.py [hydra args]
+
+Sampling: `install(..., device_inference=True)` (shell: `--device-inference` in front of the checkout) also replaces
+Experiment.inference_fn -- the reference's per-step host loop -- by se3_diffusion_amd.inference.inference_fn, the same
+signature and return value on the device-resident, hipGraph-replayed sampler:
+
+    python -m se3_diffusion_amd.dropin --device-inference /path/to/se3_diffusion experiments/inference_se3_diffusion.py
 """
 from __future__ import annotations
 
@@ -31,12 +37,16 @@ _BINDINGS = {
 _RIGID = {"openfold.utils.rigid_utils": "se3_diffusion_amd.openfold.utils.rigid_utils"}
 
 
-def install(reference_root: str | None = None, replace_rigid_utils: bool = False, patch_all_atom: bool = True):
+def install(reference_root: str | None = None, replace_rigid_utils: bool = False, patch_all_atom: bool = True,
+            device_inference: bool = False):
     """Bind the reference's hot-path module paths to the HIP implementations.  Idempotent.
 
     replace_rigid_utils: also bind openfold.utils.rigid_utils to the eigh-free Rigid/Rotation of this
     package (only the subset of SURVEY.md 8a M14 is implemented; the reference's offline data
-    pipeline uses more of that file, so the default keeps the reference's)."""
+    pipeline uses more of that file, so the default keeps the reference's).
+
+    device_inference: import experiments.train_se3_diffusion (after the bindings are in place) and set its
+    Experiment.inference_fn to inference.inference_fn.  Off by default: the reference's own loop stays."""
     if reference_root is not None:
         reference_root = os.path.abspath(reference_root)
         if not os.path.isdir(os.path.join(reference_root, "experiments")):
@@ -61,15 +71,22 @@ def install(reference_root: str | None = None, replace_rigid_utils: bool = False
             ref_all_atom.compute_backbone = ours.compute_backbone     # kills the per-call host round trip
         except ImportError:
             sys.modules.setdefault("data.all_atom", importlib.import_module("se3_diffusion_amd.data.all_atom"))
+    if device_inference:
+        from . import inference
+        tr = importlib.import_module("experiments.train_se3_diffusion")
+        tr.Experiment.inference_fn = inference.inference_fn
     return sorted(table)
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
+    device_inference = bool(argv) and argv[0] == "--device-inference"
+    if device_inference:
+        argv = argv[1:]
     if len(argv) < 2:
-        raise SystemExit("usage: python -m se3_diffusion_amd.dropin <reference_root> <script.py> [args...]")
+        raise SystemExit("usage: python -m se3_diffusion_amd.dropin [--device-inference] <reference_root> <script.py> [args...]")
     root, script = argv[0], argv[1]
-    install(root)
+    install(root, device_inference=device_inference)
     sys.argv = [script] + argv[2:]
     os.chdir(root)
     runpy.run_path(os.path.join(root, script) if not os.path.isabs(script) else script, run_name="__main__")

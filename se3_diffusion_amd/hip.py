@@ -236,6 +236,7 @@ _SIGS = {
     "fd_se3_reverse_step_f32": "ppppppiiddpdddiiips",
     "fd_se3_reverse_step_net": "ppppppiiddpdddiiips",
     "fd_sample_advance": "ppppilpipps",
+    "fd_sample_record": "ppppp" + "S" + "piili" + "pppp" + "s",
     "fd_dsm_loss": "Ss",
     "fd_adam_step": "pppplffffffs",
 }

@@ -36,16 +36,29 @@ def _f64(x, dev):
 
 @torch.no_grad()
 def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_condition=True, center=True,
-           generator=None, noise_fn=None, return_traj=False, use_graph=False, stats=None):
+           generator=None, noise_fn=None, return_traj=False, use_graph=False, stats=None, record=None):
     """Run the reverse process on `feats` (from init_feats).  noise_fn(step, shape) -> (z_rot, z_trans) injects
     draws (e.g. the numpy stream, for trajectory parity); default draws on the device.
-    Returns dict(rigids [B,N,7], atom37 [B,N,37,3], psi, (rigid_traj list)).  `stats` (a dict) receives loop_ms = device
-    time of the reverse loop itself (HIP events; excludes the one-off warm-up + graph capture) and its step count.
+    Returns dict(rigids [B,N,7], atom37 [B,N,37,3], psi, (return_traj: rigid_traj, a list of per-step frames)).  `stats` (a dict)
+    receives loop_ms = device time of the reverse loop itself (HIP events; excludes the one-off warm-up + graph capture) and its
+    step count.
 
     Random stream: with device-drawn noise the graph path (options.sampler_device_steps) fills the draws of 50 steps with ONE
     normal_ launch on a [50, 2, B, N, 3] buffer, the eager path draws [2, B, N, 3] per step: for one generator seed the two paths
     consume the Philox stream differently and give different (equally distributed) trajectories.  Injected noise (noise_fn) is
-    consumed in step order on both paths -- that is what the trajectory parity tests compare."""
+    consumed in step order on both paths -- that is what the trajectory parity tests compare.
+
+    record="reference": what Experiment.inference_fn(aux_traj=True) returns (train_se3_diffusion.py:782-818), recorded on the
+    device by ONE extra launch per step (fd_sample_record, captured with the step) into buffers allocated once -- the result gains
+    prot_traj [T,B,N,37,3], rigid_traj [T+1,B,N,7], trans_traj [T,B,N,3], rigid_0_traj [T,B,N,37,3] (device tensors, index 0 = the
+    final structure, like the reference's flipped arrays) and psi_pred [1,B,N,2].  record="prot": prot_traj only (aux_traj=False).
+    Two reference quirks are kept: the final step (t == min_t, :778-780) refreshes neither rigid_pred nor the masks, so
+    trans_traj[0] and the frames of rigid_0_traj[0] come from the previous step's prediction while psi is the fresh one; padded
+    rows (res_mask == 0) get zeros in trans_traj but real atoms in prot_traj."""
+    if record not in (None, "reference", "prot"):
+        raise ValueError(f"record={record!r}: expected None, 'reference' or 'prot'")
+    if record == "reference" and return_traj:
+        raise ValueError("return_traj and record='reference' both define rigid_traj: ask for one of them")
     dev = feats["rigids_t"].device
     B, N = feats["res_mask"].shape
     steps = np.linspace(min_t, 1.0, num_t)[::-1]
@@ -74,6 +87,16 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
     all_tp = torch.tensor(np.stack([[float(so3.diffusion_coef(t)), float(r3.b_t(t))] for t in steps]),
                           dtype=torch.float64).to(dev)
     step_of = {float(t): i for i, t in enumerate(steps)}
+
+    rec = None
+    if record is not None:
+        rec = _record_buffers(record == "reference", len(steps), B, N, dev, st)
+
+    def record_step(out, pred, slot_ptr, slot):
+        """this step's slice of the recorded trajectories: frames after the step, x0 prediction `pred`, psi of forward `out`"""
+        lib.call("fd_sample_record", st["rigids_t"], _f32c(pred["rigids"]) if rec["aux"] else None, _f32c(out["psi"]),
+                 rec["fixed"], rec["res"], rec["hc"], slot_ptr, slot, len(steps), B * N, int(rec["aux"]),
+                 rec["rigid_traj"], rec["bb_t"], rec["bb_0"], rec["trans_0"])
 
     def set_t(t):
         st["t"].fill_(float(t))
@@ -122,6 +145,15 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
         diffuser.reverse_device(st["rigids_t"], out["rot_score"], out["trans_score"], 0.5, dt, diffuse_mask=diffuse_mask,
                                 center=center, noise_scale=noise_scale, noise=(z_rot, z_trans), tparams=tparams,
                                 out=st["rigids_t"])
+        if rec is not None:
+            # the step index: fd_sample_advance's counter (already advanced: -1), else the sampler's own device int (graph replays
+            # behind host-issued fill_ / copy_, and the warm-up steps: slot 0, which the first real step overwrites), else the integer
+            if adv is not None:
+                record_step(out, out, adv["counter"], -1)
+            elif rec["slot"] is not None:
+                record_step(out, out, rec["slot"], 0)
+            else:
+                record_step(out, out, None, rec["i"])
         return out
 
     try:
@@ -143,6 +175,8 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
         if use_graph and lib.is_device and n_rev > 3:
             # warm up on a side stream (allocator, lazily-built constant tables), then capture one step
             saved = {k: st[k].clone() for k in ("rigids_t", "sc_ca_t")}
+            if rec is not None:
+                rec["slot"] = torch.zeros(1, dtype=torch.int32, device=dev)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -184,6 +218,11 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
                 else:
                     set_t(t)
                     draw(i)
+                    if rec is not None:
+                        if graph is not None:
+                            rec["slot"].fill_(i)
+                        else:
+                            rec["i"] = i
                 if graph is not None:
                     graph.replay()
                     out = cap_out
@@ -192,9 +231,13 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
                 psi = out["psi"]               # (the torsion head's output of the latest forward: no copy per step)
             else:
                 # reference quirk kept: the final forward still carries the previous step's t (train_se3_diffusion.py:778-779)
+                pred = out                     # (graph mode: the captured step's static output, which this eager forward leaves alone)
                 out = model(st)
                 st["rigids_t"].copy_(out["rigids"])
                 psi = out["psi"]
+                if rec is not None:
+                    # reference quirk kept (:778-790): rigid_pred is still the previous step's prediction, psi is the fresh one
+                    record_step(out, pred, None, i)
             if return_traj:
                 traj.append(st["rigids_t"].clone())
         if stats is not None and lib.is_device:
@@ -215,4 +258,49 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
     res = dict(rigids=st["rigids_t"], atom37=atom37, psi=psi)
     if return_traj:
         res["rigid_traj"] = traj
+    if rec is not None:
+        # atoms 5..36 of the reference's atom37 arrays are exactly zero (all_atom.compute_backbone): one scatter into zeros
+        res["prot_traj"] = _atom37_of(rec["bb_t"])
+        if rec["aux"]:
+            res.update(rigid_traj=rec["rigid_traj"], trans_traj=rec["trans_0"], rigid_0_traj=_atom37_of(rec["bb_0"]),
+                       psi_pred=psi[None])
     return res
+
+
+def _f32c(x):
+    return x if x.dtype == torch.float32 and x.is_contiguous() else x.to(torch.float32).contiguous()
+
+
+def _atom37_of(bb5):
+    a37 = torch.zeros(bb5.shape[:-2] + (37, 3), dtype=bb5.dtype, device=bb5.device)
+    a37[..., :5, :] = bb5
+    return a37
+
+
+def record_bytes(aux, T, B, N):
+    """device memory of the recording buffers of sample(record=...)"""
+    per_row = (7 + 15 + 15 + 3) if aux else 15
+    return 4 * (T * B * N * per_row + (B * N * 7 if aux else 0))
+
+
+def _record_buffers(aux, T, B, N, dev, st):
+    """The preallocated trajectories fd_sample_record writes, checked against free memory BEFORE the loop (a failed
+    allocation inside a graph capture is much harder to read)."""
+    from . import trunk
+    if T < 2:
+        raise ValueError(f"recording needs at least one reverse step in front of the final one (num_t={T}): the reference's loop "
+                         "itself fails there with an unbound rigid_pred")
+    need = record_bytes(aux, T, B, N)
+    if dev.type == "cuda":
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        if need > free:
+            raise RuntimeError(f"recording a trajectory of T={T}, B={B}, N={N} needs {need / 1e6:.0f} MB of device memory "
+                               f"({T}*{B}*{N}*{(7 + 15 + 15 + 3) if aux else 15}*4 bytes), {free / 1e6:.0f} MB are free")
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    rec = dict(aux=aux, slot=None, i=0, hc=trunk.head_const(), bb_t=new(T, B, N, 5, 3),
+               rigid_traj=None, bb_0=None, trans_0=None, fixed=None, res=None)
+    if aux:
+        rec.update(rigid_traj=new(T + 1, B, N, 7), bb_0=new(T, B, N, 5, 3), trans_0=new(T, B, N, 3),
+                   fixed=st["fixed_mask"].to(torch.float32).contiguous(), res=st["res_mask"].to(torch.float32).contiguous())
+        rec["rigid_traj"][T].copy_(st["rigids_t"])         # the starting frames (train_se3_diffusion.py:748)
+    return rec

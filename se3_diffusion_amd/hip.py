@@ -80,6 +80,7 @@ class FdLossDesc(Structure):
 
 
 class FdEdgeMlpDesc(Structure):
+    __slots__ = ()           # (a misspelt field raises instead of becoming a Python attribute)
     _fields_ = [
         ("x", c_void_p), ("img", c_void_p), ("p1", c_void_p), ("q1", c_void_p), ("bias2", c_void_p),
         ("save1", c_void_p), ("save2", c_void_p),
@@ -100,6 +101,7 @@ EDGE_MLP_IMAGE_BYTES = 124 * 12288
 
 
 class FdEdgeEmbedDesc(Structure):
+    __slots__ = ()           # (a misspelt field raises instead of becoming a Python attribute)
     _fields_ = [
         ("seq_idx", c_void_p), ("sc_ca", c_void_p), ("idenom", c_void_p), ("dg_lower", c_void_p), ("dg_upper", c_void_p),
         ("img", c_void_p), ("p", c_void_p), ("q", c_void_p), ("bias2", c_void_p), ("bias3", c_void_p),
@@ -114,6 +116,7 @@ EDGE_EMBED_IMAGE_BYTES = 24 * 12288
 
 
 class FdEdgeEmbedBwdDesc(Structure):
+    __slots__ = ()           # (a misspelt field raises instead of becoming a Python attribute)
     _fields_ = [
         ("dy", c_void_p), ("h3", c_void_p), ("mean", c_void_p), ("rstd", c_void_p), ("gamma", c_void_p), ("rowscale", c_void_p),
         ("h2", c_void_p), ("h1", c_void_p), ("img", c_void_p), ("dh3", c_void_p), ("dh2", c_void_p), ("dh1", c_void_p),
@@ -125,6 +128,7 @@ class FdEdgeEmbedBwdDesc(Structure):
 EDGE_EMBED_BWD_IMAGE_BYTES = 16 * 12288
 
 class FdLnGemmDesc(Structure):
+    __slots__ = ()           # (a misspelt field raises instead of becoming a Python attribute)
     _fields_ = [
         ("x", c_void_p), ("ldx", c_long), ("gamma", c_void_p), ("beta", c_void_p), ("ln_rowscale", c_void_p),
         ("ln_out", c_void_p), ("ld_ln_out", c_long), ("W", c_void_p), ("ldw", c_long), ("bias", c_void_p),
@@ -137,6 +141,7 @@ PAIR_DW_MAX_ITEMS = 8
 
 
 class FdPairDwItem(Structure):
+    __slots__ = ()           # (a misspelt field raises instead of becoming a Python attribute)
     _fields_ = [
         ("A", c_void_p), ("lda", c_long), ("A_add", c_void_p), ("ld_add", c_long), ("B", c_void_p), ("ldb", c_long),
         ("C", c_void_p), ("ldc", c_long), ("a_colsum", c_void_p), ("trans", c_int), ("a_bands", c_int), ("b_cols", c_int),
@@ -151,6 +156,7 @@ GROUP_DW_MAX_ITEMS = 32
 
 
 class FdGroupDwItem(Structure):
+    __slots__ = ()           # (a misspelt field raises instead of becoming a Python attribute)
     _fields_ = [("A", c_void_p), ("B", c_void_p), ("C", c_void_p), ("a_colsum", c_void_p),
                 ("lda", c_int), ("ldb", c_int), ("ldc", c_int), ("n_out", c_int), ("k_in", c_int)]
 
@@ -169,6 +175,23 @@ def _ptr(t, off=0):
     if isinstance(t, tuple):
         t, off = t
     return t.data_ptr() + t.element_size() * int(off)
+
+
+def fill_ptrs(desc, **fields):
+    """Pointer fields of a fresh descriptor by name: desc.<name> = address of a tensor, or of (tensor, element offset[, ...]) -- a
+    matrix view --; None leaves the field null.  Returns the tensors (FdLib.launch takes the stream from them)."""
+    tens = []
+    for name, t in fields.items():
+        if t is None:
+            continue
+        if type(t) is tuple:
+            off = t[1]
+            t = t[0]
+            setattr(desc, name, t.data_ptr() + t.element_size() * int(off))
+        else:
+            setattr(desc, name, t.data_ptr())
+        tens.append(t)
+    return tens
 
 
 # Signature codes: p = device pointer (tensor | (tensor, elem_offset) | None), i = int, l = long,
@@ -357,21 +380,36 @@ class FdLib:
         for x in (bias, resid, gate, rowscale):
             if x is not None:
                 tens.append(x[0] if isinstance(x, tuple) else x)
-        stream = self._stream(tens)
-        prof = self.gemm_profile
-        if prof is not None and self.is_device:
-            d.tile = self.cdll.fd_gemm_plan(ctypes.byref(d))
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-            self._check(self.cdll.fd_gemm(ctypes.byref(d), stream), "fd_gemm")
-            e1.record()
-            prof.append((d.tile, d.a_cs == 1, d.b_rs == 1, 2.0 * d.M * d.N * d.K * max(1, batch), e0, e1,
-                         (d.M, d.N, d.K, max(1, batch), int(bool(d.gate)), d.beta, int(bool(d.pair_p)), d.ksplit)))
-            return
-        self._check(self.cdll.fd_gemm(ctypes.byref(d), stream), "fd_gemm")
+        profile = None
+        if self.gemm_profile is not None and self.is_device:
+            d.tile = self.cdll.fd_gemm_plan(ctypes.byref(d))      # (the record carries the tile fd_gemm will pick)
+            profile = (d.tile, d.a_cs == 1, d.b_rs == 1, 2.0 * d.M * d.N * d.K * max(1, batch),
+                       (d.M, d.N, d.K, max(1, batch), int(bool(d.gate)), d.beta, int(bool(d.pair_p)), d.ksplit))
+        self.launch("fd_gemm", d, tens, profile)
 
-    gemm_profile = None  # set to a list to record (tile, a_kc, b_kc, flops, ev0, ev1) per fd_gemm launch
+    # -- descriptor launches -----------------------------------------------
+    gemm_profile = None  # set to a list to record (tile, a_kc, b_kc, flops, ev0, ev1, shape8) per profiled launch
+
+    @property
+    def profiling(self):
+        """Are launches being recorded?  (callers build the `profile` argument of launch() only then)"""
+        return self.gemm_profile is not None and self.is_device
+
+    def launch(self, name, desc, tensors, profile=None):
+        """Entry point `name`(&desc, stream) on the current stream of `tensors`' device.  profile = (tile code, a_kc, b_kc, flops,
+        shape8), to be given only while self.profiling: the launch is then bracketed by two timing events and recorded in
+        gemm_profile."""
+        stream = self._stream(tensors)
+        fn = getattr(self.cdll, name)
+        if profile is None:
+            self._check(fn(ctypes.byref(desc), stream), name)
+            return
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        self._check(fn(ctypes.byref(desc), stream), name)
+        e1.record()
+        self.gemm_profile.append(profile[:4] + (e0, e1, profile[4]))
 
 
 _PRODUCT: FdLib | None = None

@@ -305,12 +305,12 @@ def ipa_fwd(P, pre, s, z, quat, trans, mask, B, N, cache=None, zb=None, out_view
     dev = z
     R, Pn = B * N, B * N * N
     proj = empty((R, LDP), dev)
-    names = ("linear_q", "linear_kv", "linear_q_points", "linear_kv_points")     # column blocks 0, 2048, 6144, 6336
     if cache is not None:
-        # static weights (sampling): the four projections of s are one GEMM over the row-concatenated weight
+        # static weights (sampling): the four projections of s (_PROJ: column blocks 0, 2048, 6144, 6336) are one GEMM over the
+        # row-concatenated weight
         if ("Wproj", pre) not in cache:
-            cache[("Wproj", pre)] = (torch.cat([P[f"{pre}.{n}.weight"] for n in names], 0).contiguous(),
-                                     torch.cat([P[f"{pre}.{n}.bias"] for n in names], 0).contiguous())
+            cache[("Wproj", pre)] = (torch.cat([P[f"{pre}.{n}.weight"] for n in _PROJ], 0).contiguous(),
+                                     torch.cat([P[f"{pre}.{n}.bias"] for n in _PROJ], 0).contiguous())
         Wp, bp = cache[("Wproj", pre)]
         ops.linear(s, mv(Wp), bp, mv(proj), R, LDP, CS)
     elif _proj_views(P, pre) is not None:
@@ -336,8 +336,7 @@ def ipa_fwd(P, pre, s, z, quat, trans, mask, B, N, cache=None, zb=None, out_view
                      and (lib().is_device or opts.flash_ipa_bwd_min_tiles <= 0))
     # (the copy serves fd_ipa_attn_fwd/bwd only: the unfused softmax kernels and both flash kernels read kp)
     kpT = empty((B, H, PQ * 3, N), dev) if opts.fused_ipa_attn and ((not flash) or (train and not flash_bwd)) else None
-    par = (not train) and not flash            # sampling, launch sequence: independent launches on a second graph branch
-    ops.fork(lambda: lib().call("fd_ipa_points_fwd", proj, quat, trans, qp, kp, vp, kpT, N, R, H, C, PQ, PV), proj, par)
+    lib().call("fd_ipa_points_fwd", proj, quat, trans, qp, kp, vp, kpT, N, R, H, C, PQ, PV)
     W40, b40 = ipa_w40(P, pre, cache)
     L = lib()
     feats = empty((R, LDF), dev)
@@ -360,26 +359,20 @@ def ipa_fwd(P, pre, s, z, quat, trans, mask, B, N, cache=None, zb=None, out_view
         A = empty((B, H, N, N), dev)
         L.gemm(proj, proj, A, N, N, C, (LDP, 1), (1, LDP), N, b_off=2048, batch=B * H, bdiv=H,
                a_bs=(N * LDP, C), b_bs=(N * LDP, 2 * C), c_bs=(H * N * N, N * N), alpha=math.sqrt(1.0 / (3 * C)))
-        if par:
-            ops.join(proj)                     # the points (and whatever else the branch carried) are there
         if fused_attn:
             # logits + softmax (A in place) + o_pair (the pair part of feats) of every query row in one launch
             L.call("fd_ipa_attn_fwd", A, zb, qp, kp, kpT, P[f"{pre}.head_weights"], mask, feats, B, N)
         else:
             L.call("fd_ipa_softmax_fwd", A, zb, qp, kp, P[f"{pre}.head_weights"], mask, B, N)
         optg = empty((R, H, PV * 3), dev)
-
-        def _pts():                            # a v_pts and o_pt: other columns of feats than a v
-            L.gemm(A, vp, optg, N, PV * 3, N, (N, 1), (H * PV * 3, 1), H * PV * 3, batch=B * H, bdiv=H,
-                   a_bs=(H * N * N, N * N), b_bs=(N * H * PV * 3, PV * 3), c_bs=(N * H * PV * 3, PV * 3))
-            L.call("fd_ipa_opt_fwd", optg, quat, trans, feats, R)
-        ops.fork(_pts, proj, par)
+        # a v_pts and o_pt: other columns of feats than a v
+        L.gemm(A, vp, optg, N, PV * 3, N, (N, 1), (H * PV * 3, 1), H * PV * 3, batch=B * H, bdiv=H,
+               a_bs=(H * N * N, N * N), b_bs=(N * H * PV * 3, PV * 3), c_bs=(N * H * PV * 3, PV * 3))
+        L.call("fd_ipa_opt_fwd", optg, quat, trans, feats, R)
         L.gemm(A, proj, feats, N, C, N, (N, 1), (LDP, 1), LDF, b_off=2048 + C, batch=B * H, bdiv=H,
                a_bs=(H * N * N, N * N), b_bs=(N * LDP, 2 * C), c_bs=(N * LDF, C))
         if not fused_attn:
             L.call("fd_ipa_opair_fwd", A, zb, feats, B, N)
-        if par:
-            ops.join(proj)
     # out_view (a matrix view, sampling): x1 goes straight into the [R, 320] buffer whose columns 256.. take skip_embed -- the
     # operand of the first transformer layer's in_proj, which then normalises the first 256 columns itself (trunk.forward)
     x1 = empty((R, CS), dev) if out_view is None else out_view[0]

@@ -228,45 +228,6 @@ def join_grad_stream():
         _SIDE["used"] = False
 
 
-# ---------------------------------------------------------------------------
-# fork / join for the sampling forward.  A lone backbone's forward is ~146 dependent launches of 5-12 us; a handful of them
-# do not depend on their neighbours (skip_embed of a block, the IPA point rotation beside q k^T, a v_pts + o_pt beside a v,
-# the backbone update beside the edge transition).  fork(fn, like) runs fn() on a second stream that first waits for the
-# current one; join(like) makes the current stream wait for it.  Under hipGraph capture (sampler.sample, use_graph) the
-# pair becomes two edges of the graph and the branch runs beside the main chain.  A Python closure keeps variable CELLS, not
-# values: a caller that rebinds a name the branch reads (trunk.forward: node, quat, trans = n3, q2, t2) would let the old tensor
-# go back to the allocator while the side stream may still be reading it -- so callers bind what the branch reads as default
-# arguments of fn and/or pass it as keep=(...); both stay referenced until the join.  Same single-caller contract as side().
-# ---------------------------------------------------------------------------
-_FORK = {"streams": {}, "pending": []}
-
-
-def fork_ok(like):
-    return bool(opts.graph_fork and like.is_cuda and lib().is_device)
-
-
-def fork(fn, like, enable=True, keep=()):
-    if not (enable and fork_ok(like)):
-        fn()
-        return
-    key = like.device.index
-    st = _FORK["streams"].get(key)
-    if st is None:
-        st = _FORK["streams"][key] = torch.cuda.Stream(device=like.device)
-    st.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(st):
-        fn()
-    _FORK["pending"].append((key, (fn, tuple(keep))))
-
-
-def join(like=None):
-    if _FORK["pending"]:
-        cur = torch.cuda.current_stream()
-        for key in {k for k, _ in _FORK["pending"]}:
-            cur.wait_stream(_FORK["streams"][key])
-        _FORK["pending"].clear()
-
-
 # smallest K_in that sends an N_out = 128 pair-row weight gradient to the 128-row split-bf16 tile (256: the edge
 # transition's; 96 would add the edge embedder's 128 x 128 / 128 x 120 layers, measured slower)
 _DW_T6_MIN_K = 256
@@ -334,25 +295,13 @@ def group_dw(items, rows, blocks=0):
     tens = []
     for t, (dy, x, dW, db, n, k) in enumerate(items):
         e = d.item[t]
-        e.A, e.B, e.C = hip._ptr(dy[0], dy[1]), hip._ptr(x[0], x[1]), hip._ptr(dW[0], dW[1])
-        e.a_colsum = None if db is None else hip._ptr(db)
+        tens += hip.fill_ptrs(e, A=dy, B=x, C=dW, a_colsum=db)
         e.lda, e.ldb, e.ldc, e.n_out, e.k_in = int(dy[2]), int(x[2]), int(dW[2]), int(n), int(k)
-        tens.extend(t_ for t_ in (dy[0], x[0], dW[0], db) if t_ is not None)
     d.nitems, d.rows, d.blocks = len(items), int(rows), int(blocks or opts.node_dw_blocks)
     L = lib()
-    stream = L._stream(tens)
-    prof = L.gemm_profile
-    if prof is not None and L.is_device:
-        # profile record (tile code 11): 2 * rows * n_out * k_in flops per item
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream())
-        L._check(L.cdll.fd_group_dw(hip.ctypes.byref(d), stream), "fd_group_dw")
-        e1.record(torch.cuda.current_stream())
-        prof.append((11, False, False, sum(2.0 * rows * it[4] * it[5] for it in items), e0, e1,
-                     (len(items), 128, int(rows), 1, 0, 0, 0, 1)))
-        return
-    L._check(L.cdll.fd_group_dw(hip.ctypes.byref(d), stream), "fd_group_dw")
+    # profile record (tile code 11): 2 * rows * n_out * k_in flops per item
+    L.launch("fd_group_dw", d, tens, (11, False, False, sum(2.0 * rows * it[4] * it[5] for it in items),
+                                      (len(items), 128, int(rows), 1, 0, 0, 0, 1)) if L.profiling else None)
 
 
 def reset_dw_queue():
@@ -423,24 +372,14 @@ def ln_linear(x, gamma, beta, W, b, out, M, N, K, *, relu=False, resid=None, ln_
     """out[M,N] = epi(LN(x)[M,K] @ W[N,K]^T + b) with LN(x) = ln_rowscale * (LayerNorm(x) * gamma + beta) formed inside the GEMM
     launch (csrc/fd_ln_gemm.hip); ln_out (a matrix view): LN(x) written out too; ln_cols: only x[:, :ln_cols] is normalised.  x, W, out, resid are matrix views."""
     d = hip.FdLnGemmDesc()
-    tens = []
-
-    def ptr(t, off=0):
-        if t is None:
-            return None
-        tens.append(t)
-        return t.data_ptr() + 4 * off
-    d.x, d.ldx = ptr(x[0], x[1]), x[2]
-    d.gamma, d.beta, d.ln_rowscale = ptr(gamma), ptr(beta), ptr(ln_rowscale)
+    tens = hip.fill_ptrs(d, x=x, gamma=gamma, beta=beta, ln_rowscale=ln_rowscale, ln_out=ln_out, W=W, bias=b, resid=resid, out=out)
+    d.ldx, d.ldw, d.ldo = x[2], W[2], out[2]
     if ln_out is not None:
-        d.ln_out, d.ld_ln_out = ptr(ln_out[0], ln_out[1]), ln_out[2]
-    d.W, d.ldw, d.bias = ptr(W[0], W[1]), W[2], ptr(b)
+        d.ld_ln_out = ln_out[2]
     if resid is not None:
-        d.resid, d.ld_resid = ptr(resid[0], resid[1]), resid[2]
-    d.out, d.ldo = ptr(out[0], out[1]), out[2]
+        d.ld_resid = resid[2]
     d.M, d.N, d.K, d.relu, d.eps, d.ln_cols = int(M), int(N), int(K), int(bool(relu)), 1e-5, int(ln_cols)
-    L = lib()
-    L._check(L.cdll.fd_ln_gemm(hip.ctypes.byref(d), L._stream(tens)), "fd_ln_gemm")
+    lib().launch("fd_ln_gemm", d, tens)
 
 
 # ---------------------------------------------------------------------------
@@ -539,51 +478,31 @@ def _edge_sched(like, stream):
 EDGE_MLP_MACS_PER_ROW = 128 * 384 + 384 * 384 + 384 * 128      # 245,760 (rounds 2-4 also ran Wf[:, :128] z: 262,144)
 
 
-def edge_mlp(x, img, out, rows, nres, *, p1=None, q1=None, bias2=None, pf=None, qf=None, gamma=None, beta=None,
-             rowscale=None, save1=None, save2=None, y=None, mean=None, rstd=None,
-             backward=False, blocks=0, ld_pq=0, ld_pqf=0, zb_out=None, zb_bias=None, mask1=None, mask2=None, gmask1=None,
-             gmask2=None, ln_y=None, ln_mean=None, ln_rstd=None, ln_gamma=None, ln_rowscale=None, dy_out=None, ln_dgamma=None,
-             ln_dbeta=None, dzb=None):
+def edge_mlp(x, img, out, rows, nres, *, backward=False, blocks=0, ld_pq=0, ld_pqf=0, **ptrs):
+    """One fd_edge_mlp launch.  ptrs: the other pointer fields of hip.FdEdgeMlpDesc by name (p1, q1, bias2, pf, qf, gamma, beta,
+    rowscale, save1, save2, y, mean, rstd, zb_out, zb_bias, mask1, mask2, gmask1, gmask2, ln_*, dy_out, dzb), tensors or None."""
     d = hip.FdEdgeMlpDesc()
-    tens = []
-    for name, t in (("x", x), ("img", img), ("p1", p1), ("q1", q1), ("bias2", bias2),
-                    ("save1", save1), ("save2", save2), ("pf", pf), ("qf", qf), ("gamma", gamma), ("beta", beta),
-                    ("rowscale", rowscale), ("y", y), ("mean", mean), ("rstd", rstd), ("out", out), ("zb_out", zb_out),
-                    ("zb_bias", zb_bias), ("mask1", mask1), ("mask2", mask2), ("gmask1", gmask1), ("gmask2", gmask2),
-                    ("ln_y", ln_y), ("ln_mean", ln_mean), ("ln_rstd", ln_rstd), ("ln_gamma", ln_gamma), ("ln_rowscale", ln_rowscale),
-                    ("dy_out", dy_out), ("ln_dgamma", ln_dgamma), ("ln_dbeta", ln_dbeta), ("dzb", dzb)):
-        setattr(d, name, None if t is None else t.data_ptr())
-        if t is not None:
-            tens.append(t)
+    tens = hip.fill_ptrs(d, x=x, img=img, out=out, **ptrs)
     d.rows, d.nres, d.backward, d.eps, d.blocks = int(rows), int(nres), int(bool(backward)), 1e-5, int(blocks or opts.edge_blocks)
     d.ld_pq, d.ld_pqf = int(ld_pq), int(ld_pqf)
     d.shape = int(opts.edge_shape)
     # shape 2 (two waves per 16-row group, csrc/fd_edge_mlp_pair.hip) exists for the inference forward only: a forced 2 applies to
     # those launches and leaves the others to the size rule; edge_pair=False keeps the size rule from picking it
-    infer_fwd = not backward and save1 is None
+    infer_fwd = not backward and ptrs.get("save1") is None
     if d.shape == 2 and not infer_fwd:
         d.shape = 0
     if d.shape == 0 and infer_fwd and not opts.edge_pair and rows <= hip.EDGE_MLP_PAIR_MAX_ROWS:
         d.shape = 4
     L = lib()
-    stream = L._stream(tens)
     # tiles of the shape the entry point will pick: 128 rows on 256 blocks (8 waves, >= EDGE_MLP_W8_MIN_ROWS rows) or 64 rows on 512
     w8 = d.shape == 8 or (d.shape == 0 and rows >= hip.EDGE_MLP_W8_MIN_ROWS)
     if opts.edge_dynamic_tiles and rows >= 4 * (128 if w8 else 64) * (d.blocks or (256 if w8 else 512)):
-        d.sched = _edge_sched(out, stream)
-    prof = L.gemm_profile
-    if prof is not None and L.is_device:
-        # same record layout as FdLib.gemm (tile code 7 = the fused edge-transition kernel); algorithmic flops of the
-        # chain: 2 * rows * (128*384 + 384*384 + 384*128) -- the residual through the final layer is an add, not a product
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L._check(L.cdll.fd_edge_mlp(hip.ctypes.byref(d), stream), "fd_edge_mlp")
-        e1.record()
-        prof.append((7, True, True, 2.0 * int(rows) * (EDGE_MLP_MACS_PER_ROW + (5120 if zb_out is not None else 0)), e0, e1,
-                     (int(rows), 128, 384, 1, int(bool(backward)), 0, 0, 1)))
-        return
-    L._check(L.cdll.fd_edge_mlp(hip.ctypes.byref(d), stream), "fd_edge_mlp")
+        d.sched = _edge_sched(out, L._stream(tens))
+    # same record layout as FdLib.gemm (tile code 7 = the fused edge-transition kernel); algorithmic flops of the
+    # chain: 2 * rows * (128*384 + 384*384 + 384*128) -- the residual through the final layer is an add, not a product
+    L.launch("fd_edge_mlp", d, tens,
+             (7, True, True, 2.0 * int(rows) * (EDGE_MLP_MACS_PER_ROW + (5120 if ptrs.get("zb_out") is not None else 0)),
+              (int(rows), 128, 384, 1, int(bool(backward)), 0, 0, 1)) if L.profiling else None)
 
 
 # ---------------------------------------------------------------------------
@@ -599,32 +518,18 @@ def edge_embed_pack(W0, W2, W4, out=None, W40=None):
 
 
 def edge_embed(seq_idx, sc_ca, idenom, dg_lower, dg_upper, img, p, q, bias2, bias3, gamma, beta, out, rows, nres, *,
-               rowscale=None, h1=None, h2=None, h3=None, mean=None, rstd=None, blocks=0, zb_out=None, zb_bias=None, mask1=None,
-               mask2=None, ld_pq=0):
+               blocks=0, ld_pq=0, **ptrs):
+    """One fd_edge_embed launch.  ptrs: the optional pointer fields of hip.FdEdgeEmbedDesc by name (rowscale, h1, h2, h3, mean, rstd,
+    zb_out, zb_bias, mask1, mask2), tensors or None."""
     d = hip.FdEdgeEmbedDesc()
-    tens = []
-    for name, t in (("seq_idx", seq_idx), ("sc_ca", sc_ca), ("idenom", idenom), ("dg_lower", dg_lower), ("dg_upper", dg_upper),
-                    ("img", img), ("p", p), ("q", q), ("bias2", bias2), ("bias3", bias3), ("gamma", gamma), ("beta", beta),
-                    ("rowscale", rowscale), ("h1", h1), ("h2", h2), ("h3", h3), ("mean", mean), ("rstd", rstd), ("out", out),
-                    ("zb_out", zb_out), ("zb_bias", zb_bias), ("mask1", mask1), ("mask2", mask2)):
-        setattr(d, name, None if t is None else t.data_ptr())
-        if t is not None:
-            tens.append(t)
+    tens = hip.fill_ptrs(d, seq_idx=seq_idx, sc_ca=sc_ca, idenom=idenom, dg_lower=dg_lower, dg_upper=dg_upper, img=img, p=p, q=q,
+                         bias2=bias2, bias3=bias3, gamma=gamma, beta=beta, out=out, **ptrs)
     d.rows, d.nres, d.eps, d.blocks = int(rows), int(nres), 1e-5, int(blocks)
     d.ld_pq = int(ld_pq)
     L = lib()
-    stream = L._stream(tens)
-    prof = L.gemm_profile
-    if prof is not None and L.is_device:
-        # profile record (tile code 8): algorithmic flops of the per-pair part: 2 * rows * (54 + 128 + 128) * 128
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L._check(L.cdll.fd_edge_embed(hip.ctypes.byref(d), stream), "fd_edge_embed")
-        e1.record()
-        prof.append((8, True, True, 2.0 * int(rows) * 310 * 128, e0, e1, (int(rows), 128, 128, 1, 0, 0, 0, 1)))
-        return
-    L._check(L.cdll.fd_edge_embed(hip.ctypes.byref(d), stream), "fd_edge_embed")
+    # profile record (tile code 8): algorithmic flops of the per-pair part: 2 * rows * (54 + 128 + 128) * 128
+    L.launch("fd_edge_embed", d, tens,
+             (8, True, True, 2.0 * int(rows) * 310 * 128, (int(rows), 128, 128, 1, 0, 0, 0, 1)) if L.profiling else None)
 
 
 def edge_embed_bwd_pack(W2, W4, out=None):
@@ -637,19 +542,13 @@ def edge_embed_bwd(dy, h3, mean, rstd, gamma, rowscale, h2, h1, img, dh3, dh2, d
                    gmask1=None):
     """The edge embedder's LayerNorm backward + dX chain in one launch (csrc/fd_edge_embed_bwd.hip)."""
     d = hip.FdEdgeEmbedBwdDesc()
-    tens = []
-    for name, t in (("dy", dy), ("h3", h3), ("mean", mean), ("rstd", rstd), ("gamma", gamma), ("rowscale", rowscale), ("h2", h2),
-                    ("h1", h1), ("img", img), ("dh3", dh3), ("dh2", dh2), ("dh1", dh1), ("dgamma", dgamma), ("dbeta", dbeta),
-                    ("gmask2", gmask2), ("gmask1", gmask1)):
-        setattr(d, name, None if t is None else t.data_ptr())
-        if t is not None:
-            tens.append(t)
+    tens = hip.fill_ptrs(d, dy=dy, h3=h3, mean=mean, rstd=rstd, gamma=gamma, rowscale=rowscale, h2=h2, h1=h1, img=img, dh3=dh3, dh2=dh2,
+                         dh1=dh1, dgamma=dgamma, dbeta=dbeta, gmask2=gmask2, gmask1=gmask1)
     d.rows, d.blocks = int(rows), int(blocks)
     L = lib()
-    stream = L._stream(tens)
     if opts.edge_dynamic_tiles and rows >= 4 * 64 * (d.blocks or 512):
-        d.sched = _edge_sched(dh3, stream)
-    L._check(L.cdll.fd_edge_embed_bwd(hip.ctypes.byref(d), stream), "fd_edge_embed_bwd")
+        d.sched = _edge_sched(dh3, L._stream(tens))
+    L.launch("fd_edge_embed_bwd", d, tens)
 
 
 # ---------------------------------------------------------------------------
@@ -666,33 +565,17 @@ def pair_dw(items, rows, blocks=0):
     assert 1 <= len(items) <= hip.PAIR_DW_MAX_ITEMS
     for t, it in enumerate(items):
         e = d.item[t]
-        for name, ld in (("A", "lda"), ("B", "ldb"), ("C", "ldc"), ("A_add", "ld_add")):
-            v = it.get(name)
-            if v is None:
-                setattr(e, name, None)
-                setattr(e, ld, 0)
-                continue
-            ten, off, stride = v
-            setattr(e, name, hip._ptr(ten, off))
-            setattr(e, ld, int(stride))
-            tens.append(ten)
-        cs = it.get("colsum")
-        e.a_colsum = None if cs is None else hip._ptr(cs)
+        add = it.get("A_add")
+        tens += hip.fill_ptrs(e, A=it["A"], B=it["B"], C=it["C"], A_add=add, a_colsum=it.get("colsum"))
+        e.lda, e.ldb, e.ldc, e.ld_add = int(it["A"][2]), int(it["B"][2]), int(it["C"][2]), 0 if add is None else int(add[2])
         e.trans = int(bool(it.get("trans", False)))
         e.a_bands = int(it.get("a_bands", 3))
         e.b_cols = int(it.get("b_cols", 0))
     d.nitems, d.rows, d.blocks = len(items), int(rows), int(blocks)
     L = lib()
-    stream = L._stream(tens)
-    prof = L.gemm_profile
-    if prof is not None and L.is_device:
+    profile = None
+    if L.profiling:
         # profile record (tile code 9): 2 * rows * 384 * 128 flops per item
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream())
-        L._check(L.cdll.fd_pair_dw(hip.ctypes.byref(d), stream), "fd_pair_dw")
-        e1.record(torch.cuda.current_stream())
         flops = sum(2.0 * int(rows) * 128 * int(it.get("a_bands", 3)) * (int(it.get("b_cols", 0)) or 128) for it in items)
-        prof.append((9, False, False, flops, e0, e1, (384, 128 * len(items), int(rows), 1, 0, 0, 0, 1)))
-        return
-    L._check(L.cdll.fd_pair_dw(hip.ctypes.byref(d), stream), "fd_pair_dw")
+        profile = (9, False, False, flops, (384, 128 * len(items), int(rows), 1, 0, 0, 0, 1))
+    L.launch("fd_pair_dw", d, tens, profile)

@@ -69,57 +69,68 @@ def et_folds_node_terms(cache, save):
     return cache is not None and not save and opts.fold_node_terms and fused_edge()
 
 
-def edge_transition_fwd(P, b, n3, z, emask, B, N, save=True, cache=None, zb_next=None, n3_ln=None, after_terms=None):
+def edge_transition_fwd(P, b, n3, z, emask, B, N, save=True, cache=None, zb_next=None):
     """z' = emask * LN(W_f (relu(W_2 relu(W_1 x)) + x) + b_f), x = [z | e_i | e_j], e = W_init n3 -- the whole pair-level
     chain in ONE launch (fd_edge_mlp): h1 / h2 never reach HBM unless the backward needs them (save).
     zb_next = (W40 [40,128], b40 [40]) of the next block's IPA: its pair projection zb = W40 z' + b40 is formed by the same
     launch from z' in registers.  Returns (z', saved, zb or None)."""
     if not fused_edge():
         return edge_transition_fwd_unfused(P, b, n3, z, emask, B, N) + (None,)
+    terms = edge_transition_terms(P, b, n3, B * N, save=save, cache=cache)
+    return edge_transition_pair(P, b, terms, n3, z, emask, B, N, save=save, cache=cache, zb_next=zb_next)
+
+
+def edge_transition_terms(P, b, n3, R, save=True, cache=None, n3_ln=None):
+    """The per-residue part of the fused edge transition: (P1, Q1, Pf, Qf, their row stride or 0 = dense, e) with
+    W [z | e_i | e_j] = W_z z + (W_i e)_i + (W_j e)_j for W = W_1 (P1, Q1 + b_1) and W = W_f (Pf, Qf + b_f).
+    n3_ln (sampling, et_folds_node_terms): n3 is not formed yet -- see below."""
     pre = f"score_model.trunk.edge_transition_{b}"
-    dev = z
-    R, Pn = B * N, B * N * N
     W1, Wf = P[f"{pre}.trunk.0.weight"], P[f"{pre}.final_layer.weight"]
-    kw = {}
     assert n3_ln is None or et_folds_node_terms(cache, save)
     if et_folds_node_terms(cache, save):
         # static weights (sampling): the per-residue terms P1 | Q1 | Pf | Qf = [W1_i; W1_j; Wf_i; Wf_j] (W_init n3 + b_init)
         # (+ b1, b_f) are ONE GEMM of n3 against a matrix folded once per trajectory (5 launches -> 1); the fused kernel
         # reads the four column blocks of its [R, 1024] output through their row stride
+        LDT = 2 * EH + 2 * CZ
         key = ("et_fold", pre)
         if key not in cache:
             Wi, bi = P[f"{pre}.initial_embed.weight"], P[f"{pre}.initial_embed.bias"]
             Wcat = torch.cat([W1[:, CZ:CZ + CE], W1[:, CZ + CE:], Wf[:, CZ:CZ + CE], Wf[:, CZ + CE:]], 0).contiguous()
-            Wfold = empty((2 * EH + 2 * CZ, CS), dev)
-            ops.linear(mv(Wcat), mv(Wi.t().contiguous()), None, mv(Wfold), 2 * EH + 2 * CZ, CS, CE)
+            Wfold = empty((LDT, CS), Wi)
+            ops.linear(mv(Wcat), mv(Wi.t().contiguous()), None, mv(Wfold), LDT, CS, CE)
             bvec = torch.cat([torch.zeros_like(P[f"{pre}.trunk.0.bias"]), P[f"{pre}.trunk.0.bias"],
                               torch.zeros_like(P[f"{pre}.final_layer.bias"]), P[f"{pre}.final_layer.bias"]]).contiguous()
-            bfold = empty((1, 2 * EH + 2 * CZ), dev)
-            ops.linear(mv(bi.view(1, CE)), mv(Wcat), bvec, mv(bfold), 1, 2 * EH + 2 * CZ, CE)
+            bfold = empty((1, LDT), Wi)
+            ops.linear(mv(bi.view(1, CE)), mv(Wcat), bvec, mv(bfold), 1, LDT, CE)
             cache[key] = (Wfold, bfold.view(-1))
         Wfold, bfold = cache[key]
-        LDT = 2 * EH + 2 * CZ
-        PQ = empty((R, LDT), dev)
+        PQ = empty((R, LDT), Wfold)
         if n3_ln is not None:
             # n3 = mask * LayerNorm(t) of the node transition, formed (and written out for the other consumers) by this launch
             t_in, g_in, b_in, rs_in, _, n3_out = n3_ln
             ops.ln_linear(mv(t_in), g_in, b_in, mv(Wfold), bfold, mv(PQ), R, LDT, CS, ln_rowscale=rs_in, ln_out=mv(n3_out))
         else:
             ops.linear(mv(n3), mv(Wfold), bfold, mv(PQ), R, LDT, CS)
-        if after_terms is not None:
-            after_terms()          # (n3 exists from here on: the caller forks the backbone update beside the pair-level launch)
-        P1, Q1, Pf, Qf = PQ[:, 0:], PQ[:, EH:], PQ[:, 2 * EH:], PQ[:, 2 * EH + CZ:]
-        kw = dict(ld_pq=LDT, ld_pqf=LDT)
-        e = None
-    else:
-        e = empty((R, CE), dev)
-        ops.linear(mv(n3), mv(P[f"{pre}.initial_embed.weight"]), P[f"{pre}.initial_embed.bias"], mv(e), R, CE, CS)
-        # node halves of the two concat-linears: W [z | e_i | e_j] = W_z z + (W_i e)_i + (W_j e)_j
-        P1 = empty((R, EH), dev); Q1 = empty((R, EH), dev); Pf = empty((R, CZ), dev); Qf = empty((R, CZ), dev)
-        ops.linear(mv(e), (W1, CZ, EH), None, mv(P1), R, EH, CE)
-        ops.linear(mv(e), (W1, CZ + CE, EH), P[f"{pre}.trunk.0.bias"], mv(Q1), R, EH, CE)
-        ops.linear(mv(e), (Wf, CZ, EH), None, mv(Pf), R, CZ, CE)
-        ops.linear(mv(e), (Wf, CZ + CE, EH), P[f"{pre}.final_layer.bias"], mv(Qf), R, CZ, CE)
+        return PQ[:, 0:], PQ[:, EH:], PQ[:, 2 * EH:], PQ[:, 2 * EH + CZ:], LDT, None
+    dev = n3
+    e = empty((R, CE), dev)
+    ops.linear(mv(n3), mv(P[f"{pre}.initial_embed.weight"]), P[f"{pre}.initial_embed.bias"], mv(e), R, CE, CS)
+    P1 = empty((R, EH), dev); Q1 = empty((R, EH), dev); Pf = empty((R, CZ), dev); Qf = empty((R, CZ), dev)
+    ops.linear(mv(e), (W1, CZ, EH), None, mv(P1), R, EH, CE)
+    ops.linear(mv(e), (W1, CZ + CE, EH), P[f"{pre}.trunk.0.bias"], mv(Q1), R, EH, CE)
+    ops.linear(mv(e), (Wf, CZ, EH), None, mv(Pf), R, CZ, CE)
+    ops.linear(mv(e), (Wf, CZ + CE, EH), P[f"{pre}.final_layer.bias"], mv(Qf), R, CZ, CE)
+    return P1, Q1, Pf, Qf, 0, e
+
+
+def edge_transition_pair(P, b, terms, n3, z, emask, B, N, save=True, cache=None, zb_next=None):
+    """The pair-level launch of the fused edge transition on the per-residue `terms` (edge_transition_terms).  Returns what
+    edge_transition_fwd returns."""
+    pre = f"score_model.trunk.edge_transition_{b}"
+    dev = z
+    Pn = B * N * N
+    P1, Q1, Pf, Qf, ld, e = terms
+    kw = {}
     zb = None
     use_zb = (opts.zb_from_edge and zb_next is not None and zb_next[0].is_contiguous() and zb_next[0].data_ptr() % 16 == 0
               and zb_next[1].data_ptr() % 16 == 0)
@@ -135,7 +146,7 @@ def edge_transition_fwd(P, b, n3, z, emask, B, N, save=True, cache=None, zb_next
     if use_zb:
         zb = empty((Pn, nw.ZB), dev)
         kw.update(zb_out=zb, zb_bias=zb_next[1])
-    ops.edge_mlp(z, img, z2, Pn, N, p1=P1, q1=Q1, bias2=P[f"{pre}.trunk.2.bias"], pf=Pf, qf=Qf,
+    ops.edge_mlp(z, img, z2, Pn, N, p1=P1, q1=Q1, bias2=P[f"{pre}.trunk.2.bias"], pf=Pf, qf=Qf, ld_pq=ld, ld_pqf=ld,
                  gamma=P[f"{pre}.layer_norm.weight"], beta=P[f"{pre}.layer_norm.bias"], rowscale=emask, **kw)
     if not save:
         return z2, None, zb
@@ -171,6 +182,28 @@ def edge_transition_fwd_unfused(P, b, n3, z, emask, B, N):
     return z2, dict(n3=n3, z=z, e=e, h1=h1, h2=h2, y=y, mean=mean, rstd=rstd, emask=emask, B=B, N=N)
 
 
+def _node_terms_bwd(G, dx, C, W, gW, bias, e, de, B, N, accumulate):
+    """Backward of the node halves of a concat-linear W [z | e_i | e_j] ([C, 384]): dx [P, C], the gradient over the pair rows, is
+    reduced to the per-residue dP (over j) and dQ (over i); gW[:, 128:256] += dP^T e, gW[:, 256:] += dQ^T e, G[bias] += column
+    sums of dQ (in the block's grouped launch, else on the side stream); de (+)= dP W_i + dQ W_j."""
+    R = B * N
+    dP = zeros((R, C), e); dQ = zeros((R, C), e)
+    lib().call("fd_pair_reduce_acc", dx, B, N, C, dP, dQ, C)
+    wi, wj = (gW, CZ, EH), (gW, CZ + CE, EH)
+    # (both products or neither: a half-accepted pair followed by the fallback would add the accepted product twice)
+    if ops.queue_dw_ok(mv(dP), mv(e), wi, R, C, CE) and ops.queue_dw_ok(mv(dQ), mv(e), wj, R, C, CE):
+        ops.queue_dw(mv(dP), mv(e), wi, R, C, CE)
+        ops.queue_dw(mv(dQ), mv(e), wj, R, C, CE, db=G[bias])
+    else:
+        def _grads():
+            ops.linear_dw(mv(dP), mv(e), wi, R, C, CE)
+            ops.linear_dw(mv(dQ), mv(e), wj, R, C, CE)
+            ops.bias_grad(mv(dQ), G[bias], R, C)
+        ops.side(_grads, (dP, dQ, e), R)
+    ops.linear_dx(mv(dP), (W, CZ, EH), mv(de), R, C, CE, beta=accumulate)
+    ops.linear_dx(mv(dQ), (W, CZ + CE, EH), mv(de), R, C, CE, beta=True)
+
+
 def edge_transition_bwd(P, G, b, sv, dz2, dz, dn3, dzb_next=None, flush_behind_launch=False):
     """dz2 [P,128] (gradient of the transition's output; None when dzb_next carries all of it) -> dz [P,128] (=), dn3 (+=).
     dzb_next = (dzb [P,40], W40 [40,128]) of the IPA block BEHIND this transition: its pair-projection term dzb W40 still has
@@ -181,6 +214,7 @@ def edge_transition_bwd(P, G, b, sv, dz2, dz, dn3, dzb_next=None, flush_behind_l
     dev = sv["z"]
     L = lib()
     W1, W2, Wf = P[f"{pre}.trunk.0.weight"], P[f"{pre}.trunk.2.weight"], P[f"{pre}.final_layer.weight"]
+    gW1, gWf = G[f"{pre}.trunk.0.weight"], G[f"{pre}.final_layer.weight"]
     z, e, h1, h2 = sv["z"], sv["e"], sv["h1"], sv["h2"]
     # which backward runs is decided by what the FORWARD saved, not by the options of this moment: the fused dX kernel gates on the
     # packed masks the fused forward wrote, and that forward's h2 save carries the residual z (h2_has_z) -- only the fused backward
@@ -189,29 +223,44 @@ def edge_transition_bwd(P, G, b, sv, dz2, dz, dn3, dzb_next=None, flush_behind_l
     h2_has_z = bool(sv.get("h2_has_z"))      # the fused forward saved h2 + [z | 0 | 0] (the operand of dWf), not h2
     assert fused or not h2_has_z, "a fused edge-transition forward needs the fused backward (its h2 save carries z)"
     fused_ln = fused and opts.fused_ln_bwd and (dzb_next is None or dzb_next[1].is_contiguous())
-    if dzb_next is not None and not fused_ln:
-        # materialise the IPA term first (streaming kernel, W40 resident in registers)
-        dzb, W40 = dzb_next
-        if dz2 is None:
-            dz2 = empty((Pn, CZ), dev)
-            L.call("fd_ipa_dz_acc", dzb, W40.contiguous(), dz2, Pn, 0)
-        else:
-            L.call("fd_ipa_dz_acc", dzb, W40.contiguous(), dz2, Pn, 1)
-    dy = empty((Pn, CZ), dev)
-    gWf = G[f"{pre}.final_layer.weight"]
-    gW1 = G[f"{pre}.trunk.0.weight"]
     grouped_dw = fused and opts.grouped_pair_dw
-    dh2 = dh1 = None
-    if fused_ln:
-        # ONE launch: (dz2 + dzb W40) -> LayerNorm backward (dgamma, dbeta) -> dy -> d2 = [h2 > 0] dy Wf -> d1 = [h1 > 0] d2 W2 ->
-        # dz = dy Wf_z + d1 W1_z; dy, d2, d1 are written once for the weight gradients and the pair reductions
+    dy = empty((Pn, CZ), dev)
+    de = empty((R, CE), dev)
+
+    def ln_bwd(dz2):
+        """dy by the separate kernels: the IPA term (streaming kernel, W40 resident in registers), then the LayerNorm backward"""
+        if dzb_next is not None:
+            acc = dz2 is not None
+            dz2 = dz2 if acc else empty((Pn, CZ), dev)
+            L.call("fd_ipa_dz_acc", dzb_next[0], dzb_next[1].contiguous(), dz2, Pn, int(acc))
+        if flush_behind_launch:
+            ops.flush_dw()
+        ops.layernorm_bwd(mv(dz2), mv(sv["y"]), P[f"{pre}.layer_norm.weight"], sv["mean"], sv["rstd"], mv(dy), Pn, CZ,
+                          rowscale=sv["emask"], dgamma=G[f"{pre}.layer_norm.weight"], dbeta=G[f"{pre}.layer_norm.bias"])
+
+    def final_layer_grads():
+        """y = Wf h2 + Wf[:, :128] z + Pf_i + Qf_j (+ bf inside Qf): dWf over the pair rows (unless it rides in the grouped launch
+        below) and the node terms"""
+        if not grouped_dw:
+            def _grads_y():
+                ops.linear_dw(mv(dy), mv(h2), mv(gWf), Pn, CZ, EH)
+                if not h2_has_z:
+                    ops.linear_dw(mv(dy), mv(z), (gWf, 0, EH), Pn, CZ, CZ)
+            ops.side(_grads_y, (dy, h2, z), Pn)
+        _node_terms_bwd(G, dy, CZ, Wf, gWf, f"{pre}.final_layer.bias", e, de, B, N, accumulate=False)
+
+    if fused:
+        # d2 = [h2 > 0] dy Wf and d1 = [h1 > 0] d2 W2, written once by the fused launch for the weight gradients and the pair
+        # reductions; its ReLU gates are the packed sign bits of the forward
         dh2 = empty((Pn, EH), dev); dh1 = empty((Pn, EH), dev)
+        dx_args = dict(save1=dh2, save2=dh1, backward=True, gmask1=sv["mh2"], gmask2=sv["mh1"])
+    if fused_ln:
+        # (i) ONE launch: (dz2 + dzb W40) -> LayerNorm backward (dgamma, dbeta) -> dy -> d2 -> d1 -> dz = dy Wf_z + d1 W1_z
         img = ops.edge_mlp_pack_bwd(Wf, W2, W1, W40=dzb_next[1] if dzb_next is not None else None)
-        gk = dict(gmask1=sv["mh2"], gmask2=sv["mh1"])
-        ops.edge_mlp(dz2, img, dz, Pn, N, save1=dh2, save2=dh1, backward=True, ln_y=sv["y"], ln_mean=sv["mean"],
-                     ln_rstd=sv["rstd"], ln_gamma=P[f"{pre}.layer_norm.weight"], ln_rowscale=sv["emask"], dy_out=dy,
+        ops.edge_mlp(dz2, img, dz, Pn, N, ln_y=sv["y"], ln_mean=sv["mean"], ln_rstd=sv["rstd"],
+                     ln_gamma=P[f"{pre}.layer_norm.weight"], ln_rowscale=sv["emask"], dy_out=dy,
                      ln_dgamma=G[f"{pre}.layer_norm.weight"], ln_dbeta=G[f"{pre}.layer_norm.bias"],
-                     dzb=dzb_next[0] if dzb_next is not None else None, **gk)
+                     dzb=dzb_next[0] if dzb_next is not None else None, **dx_args)
         if flush_behind_launch:
             # the grouped node-level weight gradients of the block BEHIND this transition (queued by the previous iteration of
             # trunk._backward) go to the side stream HERE, behind the full-chip kernel just issued: their launch then shares the
@@ -219,85 +268,46 @@ def edge_transition_bwd(P, G, b, sv, dz2, dz, dn3, dzb_next=None, flush_behind_l
             # every CU, in front of this kernel (0.2-0.25 ms per block in profiles/r05_step_gap.txt: the 4-byte memset that
             # zeroes the tile counter waited 200 us for a CU)
             ops.flush_dw()
+        final_layer_grads()
+    elif fused:
+        # (ii) the separate LayerNorm backward, then the dX chain in one launch (fd_edge_mlp with the transposed weight image)
+        ln_bwd(dz2)
+        final_layer_grads()
+        ops.edge_mlp(dy, _edge_mlp_image(P, pre, None, backward=True), dz, Pn, N, **dx_args)
     else:
-        if flush_behind_launch:
-            ops.flush_dw()
-        ops.layernorm_bwd(mv(dz2), mv(sv["y"]), P[f"{pre}.layer_norm.weight"], sv["mean"], sv["rstd"], mv(dy), Pn, CZ,
-                          rowscale=sv["emask"], dgamma=G[f"{pre}.layer_norm.weight"], dbeta=G[f"{pre}.layer_norm.bias"])
-    # y = Wf h2 + Wf[:, :128] z + Pf_i + Qf_j (+bf inside Qf)
-    if not grouped_dw:
-        def _grads_y():
-            ops.linear_dw(mv(dy), mv(h2), mv(gWf), Pn, CZ, EH)
-            if not h2_has_z:
-                ops.linear_dw(mv(dy), mv(z), (gWf, 0, EH), Pn, CZ, CZ)
-        ops.side(_grads_y, (dy, h2, z), Pn)
-    dPf = zeros((R, CZ), dev); dQf = zeros((R, CZ), dev)
-    L.call("fd_pair_reduce_acc", dy, B, N, CZ, dPf, dQf, CZ)
-    def _grads_f():
-        ops.linear_dw(mv(dPf), mv(e), (gWf, CZ, EH), R, CZ, CE)
-        ops.linear_dw(mv(dQf), mv(e), (gWf, CZ + CE, EH), R, CZ, CE)
-        ops.bias_grad(mv(dQf), G[f"{pre}.final_layer.bias"], R, CZ)
-    # (both products or neither: a half-accepted pair followed by the fallback would add the accepted product twice)
-    if (ops.queue_dw_ok(mv(dPf), mv(e), (gWf, CZ, EH), R, CZ, CE)
-            and ops.queue_dw_ok(mv(dQf), mv(e), (gWf, CZ + CE, EH), R, CZ, CE)):
-        ops.queue_dw(mv(dPf), mv(e), (gWf, CZ, EH), R, CZ, CE)
-        ops.queue_dw(mv(dQf), mv(e), (gWf, CZ + CE, EH), R, CZ, CE, db=G[f"{pre}.final_layer.bias"])
-    else:
-        ops.side(_grads_f, (dPf, dQf, e), R)
-    de = empty((R, CE), dev)
-    ops.linear_dx(mv(dPf), (Wf, CZ, EH), mv(de), R, CZ, CE)
-    ops.linear_dx(mv(dQf), (Wf, CZ + CE, EH), mv(de), R, CZ, CE, beta=True)
-    if fused:
-        if not fused_ln:
-            # the dX chain in one launch: d2 = [h2 > 0] dy Wf, d1 = [h1 > 0] d2 W2, dz = dy Wf_z + d1 W1_z (fd_edge_mlp with
-            # the transposed weight image); d2 / d1 are written once, for the weight-gradient GEMMs and the pair reductions
-            dh2 = empty((Pn, EH), dev); dh1 = empty((Pn, EH), dev)
-            gk = dict(gmask1=sv["mh2"], gmask2=sv["mh1"])
-            ops.edge_mlp(dy, _edge_mlp_image(P, pre, None, backward=True), dz, Pn, N, save1=dh2, save2=dh1, backward=True, **gk)
-        if grouped_dw:
-            # every pair-row weight gradient of the transition in ONE grouped launch (fd_pair_dw): dW2 = d2^T h1 as three
-            # 384 x 128 tiles (+ its bias gradient), dW1[:, z part] = d1^T z, dWf = dy^T (h2 + [z | 0]) stored transposed (the
-            # fused forward saved that sum: no A_add)
-            gW2, gb2 = G[f"{pre}.trunk.2.weight"], G[f"{pre}.trunk.2.bias"]
-            items = [dict(A=(dh2, 0, EH), B=(h1, CZ * j, EH), C=(gW2, CZ * j, EH), colsum=gb2 if j == 0 else None)
-                     for j in range(3)]
-            items.append(dict(A=(dh1, 0, EH), B=(z, 0, CZ), C=(gW1, 0, EH)))
-            it = dict(A=(h2, 0, EH), B=(dy, 0, CZ), C=(gWf, 0, EH), trans=True)
-            if not h2_has_z:
-                it["A_add"] = (z, 0, CZ)
-            items.append(it)
-            # On the side stream the grouped kernel takes 160 of the 256 CUs (32 row ranges x 5 tiles): it then runs 1.6x longer
-            # but BESIDE the ~100 latency-bound node-level / IPA launches the main stream issues next, instead of holding
-            # every CU while they queue behind it (27.1 -> 26.5 ms per step; 128 / 192 / 256 blocks: 26.6 / 26.6 / 27.1)
-            nblk = opts.pair_dw_blocks if ops.side_active(dh2, Pn) else 0
-            ops.side(lambda: ops.pair_dw(items, Pn, blocks=nblk), (dh2, dh1, h1, h2, z, dy), Pn)
-        else:
-            _lin_grads(G, f"{pre}.trunk.2.weight", f"{pre}.trunk.2.bias", mv(dh2), mv(h1), Pn, EH, EH)
-        del dh2
-    else:
+        # (iii) the forward ran as a GEMM sequence: so does the backward, gated on the saved h2 / h1
+        ln_bwd(dz2)
+        final_layer_grads()
         ops.linear_dx(mv(dy), (Wf, 0, EH), mv(dz), Pn, CZ, CZ)                     # dz = dy Wf_z
         dh2 = empty((Pn, EH), dev)
         ops.linear_dx(mv(dy), mv(Wf), mv(dh2), Pn, CZ, EH, gate=mv(h2))
         _lin_grads(G, f"{pre}.trunk.2.weight", f"{pre}.trunk.2.bias", mv(dh2), mv(h1), Pn, EH, EH)
         dh1 = empty((Pn, EH), dev)
         ops.linear_dx(mv(dh2), mv(W2), mv(dh1), Pn, EH, EH, gate=mv(h1))
-        del dh2
-    if not grouped_dw:
-        ops.side(lambda: ops.linear_dw(mv(dh1), mv(z), (gW1, 0, EH), Pn, EH, CZ), (dh1, z), Pn)
-    dP1 = zeros((R, EH), dev); dQ1 = zeros((R, EH), dev)
-    L.call("fd_pair_reduce_acc", dh1, B, N, EH, dP1, dQ1, EH)
-    def _grads_1():
-        ops.linear_dw(mv(dP1), mv(e), (gW1, CZ, EH), R, EH, CE)
-        ops.linear_dw(mv(dQ1), mv(e), (gW1, CZ + CE, EH), R, EH, CE)
-        ops.bias_grad(mv(dQ1), G[f"{pre}.trunk.0.bias"], R, EH)
-    if (ops.queue_dw_ok(mv(dP1), mv(e), (gW1, CZ, EH), R, EH, CE)
-            and ops.queue_dw_ok(mv(dQ1), mv(e), (gW1, CZ + CE, EH), R, EH, CE)):
-        ops.queue_dw(mv(dP1), mv(e), (gW1, CZ, EH), R, EH, CE)
-        ops.queue_dw(mv(dQ1), mv(e), (gW1, CZ + CE, EH), R, EH, CE, db=G[f"{pre}.trunk.0.bias"])
+    # the pair-row weight gradients still open: dW2 behind a fused launch, dW1's z part (and dWf in the grouped launch)
+    if grouped_dw:
+        # every pair-row weight gradient of the transition in ONE grouped launch (fd_pair_dw): dW2 = d2^T h1 as three
+        # 384 x 128 tiles (+ its bias gradient), dW1[:, z part] = d1^T z, dWf = dy^T (h2 + [z | 0]) stored transposed (the
+        # fused forward saved that sum: no A_add)
+        gW2, gb2 = G[f"{pre}.trunk.2.weight"], G[f"{pre}.trunk.2.bias"]
+        items = [dict(A=(dh2, 0, EH), B=(h1, CZ * j, EH), C=(gW2, CZ * j, EH), colsum=gb2 if j == 0 else None)
+                 for j in range(3)]
+        items.append(dict(A=(dh1, 0, EH), B=(z, 0, CZ), C=(gW1, 0, EH)))
+        it = dict(A=(h2, 0, EH), B=(dy, 0, CZ), C=(gWf, 0, EH), trans=True)
+        if not h2_has_z:
+            it["A_add"] = (z, 0, CZ)
+        items.append(it)
+        # On the side stream the grouped kernel takes 160 of the 256 CUs (32 row ranges x 5 tiles): it then runs 1.6x longer
+        # but BESIDE the ~100 latency-bound node-level / IPA launches the main stream issues next, instead of holding
+        # every CU while they queue behind it (27.1 -> 26.5 ms per step; 128 / 192 / 256 blocks: 26.6 / 26.6 / 27.1)
+        nblk = opts.pair_dw_blocks if ops.side_active(dh2, Pn) else 0
+        ops.side(lambda: ops.pair_dw(items, Pn, blocks=nblk), (dh2, dh1, h1, h2, z, dy), Pn)
     else:
-        ops.side(_grads_1, (dP1, dQ1, e), R)
-    ops.linear_dx(mv(dP1), (W1, CZ, EH), mv(de), R, EH, CE, beta=True)
-    ops.linear_dx(mv(dQ1), (W1, CZ + CE, EH), mv(de), R, EH, CE, beta=True)
+        if fused:
+            _lin_grads(G, f"{pre}.trunk.2.weight", f"{pre}.trunk.2.bias", mv(dh2), mv(h1), Pn, EH, EH)
+        ops.side(lambda: ops.linear_dw(mv(dh1), mv(z), (gW1, 0, EH), Pn, EH, CZ), (dh1, z), Pn)
+    del dh2
+    _node_terms_bwd(G, dh1, EH, W1, gW1, f"{pre}.trunk.0.bias", e, de, B, N, accumulate=True)
     if not fused:
         ops.linear_dx(mv(dh1), (W1, 0, EH), mv(dz), Pn, EH, CZ, beta=True)          # dz += dh1 W1_z
     _lin_grads(G, f"{pre}.initial_embed.weight", f"{pre}.initial_embed.bias", mv(de), mv(sv["n3"]), R, CE, CS)
@@ -450,15 +460,6 @@ def _tfmr_layers(P, b):
     return n
 
 
-def _fork_bb_update(P, b, n3, dmask, quat, trans, R, box, like):
-    """the backbone update beside the edge transition (sampling): the tensors the branch reads are bound HERE, not looked up
-    through the caller's loop variables when the side stream runs (ops.fork), and it keeps its own profiling range"""
-    def run(n3=n3, quat=quat, trans=trans):
-        with rng(f"node_transition_{b}.fwd"):
-            box.update(r=bb_update_fwd(P, b, n3, dmask.view(-1), quat, trans, R))
-    ops.fork(run, like, keep=(n3, quat, trans, dmask))
-
-
 def forward(P, feats, num_blocks, dconf=(0.1, 0.1, 20.0, 0.1, 1.5, 1000), tfmr_bool_mask=False, save=True, cache=None,
             sc_ca_out=None):
     """ScoreNetwork.forward.  Returns (outputs, saved-for-backward or None).  `cache`: see _cached (no-grad only)."""
@@ -512,7 +513,7 @@ def forward(P, feats, num_blocks, dconf=(0.1, 0.1, 20.0, 0.1, 1.5, 1000), tfmr_b
     # [LayerNorm input | skip] buffer; block b's buffer is the column range [320 b, 320 b + 320) of one [R, 320 nb] tensor
     # (its first 256 columns are written later, by the block's IPA linear_out)
     cat_all = None
-    if (cache is not None and not save and num_blocks > 1 and opts.merge_skip_embed and not ops.fork_ok(mask)
+    if (cache is not None and not save and num_blocks > 1 and opts.merge_skip_embed
             and all(_tfmr_layers(P, b) >= 1 for b in range(num_blocks))
             and ops.ln_linear_ok((node, 0, TD), (node, 0, TD), R, 3 * TD, TD)):
         tp = "score_model.trunk"
@@ -536,13 +537,11 @@ def forward(P, feats, num_blocks, dconf=(0.1, 0.1, 20.0, 0.1, 1.5, 1000), tfmr_b
         fold6 = fold1 and b < num_blocks - 1 and et_folds_node_terms(cache, save)
         # cat: matrix view (tensor, column offset, row stride) of the block's [LayerNorm input | skip] buffer
         cat = ((cat_all, b * TD, num_blocks * TD) if cat_all is not None else (empty((R, TD), dev), 0, TD)) if fold1 else None
-        ops.join(node)          # the backbone update of the block in front (sampling: a second graph branch)
         if fold1 and cat_all is None:
-            # skip_embed depends on nothing but the embedder's output: beside the IPA launches (its own columns of `cat`)
+            # skip_embed (of the embedder's output) into its own columns of `cat`
             tp = "score_model.trunk"
-            ops.fork(lambda b=b, cat=cat: ops.linear(mv(init_node), mv(P[f"{tp}.skip_embed_{b}.weight"]),
-                                                     P[f"{tp}.skip_embed_{b}.bias"], (cat[0], cat[1] + CS, cat[2]), R, 64, CS), node,
-                     keep=(init_node, cat[0]))
+            ops.linear(mv(init_node), mv(P[f"{tp}.skip_embed_{b}.weight"]), P[f"{tp}.skip_embed_{b}.bias"],
+                       (cat[0], cat[1] + CS, cat[2]), R, 64, CS)
         with rng(f"ipa_{b}.fwd"):
             x1, sv_ipa = nw.ipa_fwd(P, pre, mv(node), z, quat, trans, mask.view(-1), B, N, cache, zb=zb,
                                     out_view=cat if fold1 else None, save=save)
@@ -550,7 +549,6 @@ def forward(P, feats, num_blocks, dconf=(0.1, 0.1, 20.0, 0.1, 1.5, 1000), tfmr_b
             pend_ln = None      # a LayerNorm whose launch is folded into its consumer's (nw.tfmr_layer_fwd)
             if fold1:
                 tp = "score_model.trunk"
-                ops.join(node)
                 u = u0 = empty((R, TD), dev)             # written by the first layer's in_proj launch
                 pend_ln = (cat, P[f"{tp}.ipa_ln_{b}.weight"], P[f"{tp}.ipa_ln_{b}.bias"], None, CS, u0)
                 sv_ln = None
@@ -570,16 +568,16 @@ def forward(P, feats, num_blocks, dconf=(0.1, 0.1, 20.0, 0.1, 1.5, 1000), tfmr_b
             pend_ln = None
         sv_et = None
         if fold6:
+            # the transition's LayerNorm runs inside the per-residue GEMM of the edge transition, which writes n3: the backbone
+            # update (which needs n3) follows that GEMM, in front of the pair-level launch
             n3_ln, sv_pn = sv_pn, None
             n3 = n3_ln[5]
-            # the backbone update needs the block's node output only: beside the edge transition, joined by the next block
-            bbo = {}
             with rng(f"edge_transition_{b}.fwd"):
-                z, sv_et, zb = edge_transition_fwd(
-                    P, b, None, z, emask, B, N, save=save, cache=cache,
-                    zb_next=nw.ipa_w40(P, f"score_model.trunk.ipa_{b + 1}", cache), n3_ln=n3_ln,
-                    after_terms=lambda b=b, n3=n3, quat=quat, trans=trans: _fork_bb_update(P, b, n3, dmask, quat, trans, R, bbo, node))
-            q2, t2, sv_bb = bbo["r"]
+                terms = edge_transition_terms(P, b, None, R, save=save, cache=cache, n3_ln=n3_ln)
+                with rng(f"node_transition_{b}.fwd"):
+                    q2, t2, sv_bb = bb_update_fwd(P, b, n3, dmask.view(-1), quat, trans, R)
+                z, sv_et, zb = edge_transition_pair(P, b, terms, n3, z, emask, B, N, save=save, cache=cache,
+                                                    zb_next=nw.ipa_w40(P, f"score_model.trunk.ipa_{b + 1}", cache))
         else:
             with rng(f"node_transition_{b}.fwd"):
                 q2, t2, sv_bb = bb_update_fwd(P, b, n3, dmask.view(-1), quat, trans, R)
@@ -591,7 +589,6 @@ def forward(P, feats, num_blocks, dconf=(0.1, 0.1, 20.0, 0.1, 1.5, 1000), tfmr_b
         node, quat, trans = n3, q2, t2
         if not save:
             stages[-1] = None
-    ops.join(node)
     with rng("heads.fwd"):
         # sampling: the heads also write the predicted CA positions where the loop keeps its self-conditioning input (sc_ca_out,
         # handed down by sampler.sample through the module): no copy launch between the forward and the reverse step

@@ -237,7 +237,7 @@ def test_record_graph_matches_eager_gpu(hip_lib, monkeypatch):
     for k, v in res[0].items():
         assert bool(torch.isfinite(v).all()), k
         assert torch.equal(res[1][k], res[2][k]), k
-        assert float((res[1][k] - v).abs().max()) < 1e-4, k      # eager vs replayed: the bound of test_sampler.py's fork test
+        assert float((res[1][k] - v).abs().max()) < 1e-4, k      # eager vs replayed (test_sampler.py's test_device_steps_match_host_steps_gpu holds the frames alone to 1e-5)
     for r in res:
         assert torch.equal(r["rigid_0_traj"][0, ..., 1, :], r["rigid_0_traj"][1, ..., 1, :])
 

@@ -626,6 +626,51 @@ int fd_dsm_loss(const FdLossDesc* desc, void* stream);
 int fd_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float bc1, float bc2, void* stream);
 
+/* ---- gradient health and the guarded optimiser step (se3_diffusion_amd/csrc/fd_optim.hip) ----
+ * No reference lines stand behind these two: the reference tests torch.isnan(loss) on the host once per step and aborts
+ * (experiments/train_se3_diffusion.py:448-454).  The torch calls they restate are torch.nn.utils.clip_grad_norm_ followed
+ * by torch.optim.Adam.step, the step taken only when every gradient element is finite -- with the norm, the decision,
+ * the step counter and the bias corrections kept on the device, so the host reads nothing back and the launches can be
+ * captured and replayed.  All sums are fp64 over per-block partials written with plain stores and added in a fixed order:
+ * bitwise reproducible for a given n.
+ *
+ * workspace: FD_OPT_WS_DOUBLES doubles of device scratch (per-block partials; launches that may run at the same time need
+ * workspaces of their own).  Both entry points follow the empty-input rule: n == 0 returns FD_OK without a launch and
+ * without touching stats / p / m / v / state. */
+#define FD_OPT_WS_DOUBLES (3 * 4096)
+#define FD_OPT_STATE_BYTES 72
+/* The optimiser's device-resident state; zero-initialised by the caller before the first step.  Counters accumulate over
+ * the calls, the remaining fields describe the latest call. */
+typedef struct FdOptState {
+  long step;          /* applied steps (the t of Adam's bias corrections) */
+  long skipped;       /* calls that left p, m, v untouched because of a non-finite gradient element */
+  long clipped;       /* applied steps whose coefficient was below 1 */
+  long nonfinite;     /* non-finite elements (inf, -inf, NaN) of the latest gradient */
+  double grad_norm;   /* L2 norm over the finite elements of the latest gradient */
+  double clip_coef;   /* min(1, max_norm / (grad_norm + 1e-6)) of the latest call; 1 without clipping and for a skipped call */
+  double max_abs;     /* max |g| over the finite elements */
+  float bc1;          /* 1 - b1^step              \  of the latest applied step: computed in fp64, */
+  float rsqrt_bc2;    /* 1 / sqrt(1 - b2^step)    /  rounded once to fp32                          */
+  float coef;         /* clip_coef rounded to fp32: the factor the update kernel applies to g */
+  int apply;          /* 1: the latest call updated p, m, v; 0: it skipped */
+} FdOptState;
+
+/* stats[4] (device) = {sum of squares over the finite elements, count of non-finite elements, max |g| over the finite elements, 0}
+ * of g[0:n] (n % 4 == 0, 16-byte aligned; zero padding adds nothing); workspace and stats 8-byte aligned.  For callers that keep torch.optim.Adam over
+ * dist.FlatGrads: take it after the all-reduce, so every rank sees the same figures. */
+int fd_grad_stats(const float* g, long n, double* workspace, double* stats, void* stream);
+
+/* The guarded fd_adam_step, three dependent launches: statistics of g; the decision
+ *   apply = !(skip_nonfinite && nonfinite > 0);
+ *   apply: step += 1, coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1, bc_i from the new step, clipped += coef < 1
+ *   else : skipped += 1 (coef = 1)
+ * written into *state (FD_OPT_STATE_BYTES of DEVICE memory, 8-byte aligned); and fd_adam_step's update on coef * g with
+ * lr / bc1 and 1/sqrt(bc2) read from the state, which touches neither p, m nor v when apply == 0.  g is NOT rewritten: it
+ * keeps the unclipped gradient (unlike clip_grad_norm_).  max_norm <= 0: no clipping.  The norm is taken over the finite
+ * elements; with skip_nonfinite == 0 a non-finite element therefore reaches its own p, m, v (and only those). */
+int fd_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
+                         double max_norm, int skip_nonfinite, double* workspace, void* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,19 +38,25 @@ def init_from_env(backend=None):
 
 
 class FlatGrads:
-    """Flat gradient buffer + one all-reduce (mean) per step."""
+    """Flat gradient buffer + one all-reduce (mean) per step.
+
+    Gradient statistics (grad_stats(), and the guarded step of optim.FlatAdam) are taken AFTER all_reduce_mean() /
+    OverlapAllReduce.finish(): the reduced buffer is the same on every rank, so every rank clips or skips alike."""
 
     def __init__(self, params):
         self.params = [p for p in params if p.requires_grad]
         n = sum(p.numel() for p in self.params)
         dev = self.params[0].device
-        self.flat = torch.zeros(n, device=dev, dtype=torch.float32)
+        # (length rounded up to a multiple of 4 with a zero tail nobody writes: fd_grad_stats reads float4s, the tail adds nothing to
+        #  its sums and at most 3 floats to the all-reduce)
+        self.flat = torch.zeros((n + 3) // 4 * 4, device=dev, dtype=torch.float32)
         self.offsets, off = [], 0
         for p in self.params:
             self.offsets.append(off)
             p.grad = self.flat[off:off + p.numel()].view_as(p)
             off += p.numel()
         self._dirty = False      # the buffer holds a gradient all_reduce_mean() already shipped (see rebind)
+        self._ws = self._stats = None
 
     def rebind(self):
         """p.grad must stay a view of the flat buffer: model.zero_grad() (set_to_none=True by default) or
@@ -91,6 +97,25 @@ class FlatGrads:
         self._dirty = True
 
 
+    def grad_stats(self, out=None):
+        """fd_grad_stats of the flat buffer: a device tensor of 4 doubles {sum of squares over the finite elements, count of
+        non-finite elements, max |g| over the finite ones, 0}, nothing read back -- for loops that keep torch.optim.Adam
+        and decide on clipping / skipping themselves.  Without `out` the result is ONE tensor owned by this object, allocated
+        at the first call and overwritten by every later one (as optim.FlatAdam.grad_stats).  Call it after
+        all_reduce_mean() / OverlapAllReduce.finish()."""
+        from . import hip
+        self.rebind()
+        if self._ws is None:
+            self._ws = torch.empty(hip.OPT_WS_DOUBLES, dtype=torch.float64, device=self.flat.device)
+        if out is None:
+            if self._stats is None:
+                self._stats = torch.zeros(4, dtype=torch.float64, device=self.flat.device)
+            out = self._stats
+        assert out.dtype == torch.float64 and out.numel() == 4 and out.is_contiguous(), "out: 4 contiguous doubles"
+        hip.get_lib().call("fd_grad_stats", self.flat, self.flat.numel(), self._ws, out)
+        return out
+
+
 class OverlapAllReduce:
     """The gradient all-reduce in parameter groups, each started as soon as the backward pass has issued the group's last
     gradient launch (trunk.backward's on_done): heads, trunk blocks nb-1 .. 0, embedder.  The groups are contiguous
@@ -101,6 +126,9 @@ class OverlapAllReduce:
         hook = OverlapAllReduce(model, opt)        # opt: optim.FlatAdam or dist.FlatGrads over model.parameters()
         model._fd_grad_ready = hook.ready          # ScoreNetwork(accumulate_into_grad=True) forwards it to the backward
         loss.backward(); hook.finish(); opt.step()
+
+    opt.grad_stats() and a guarded opt.step() come after finish(): only then does the buffer hold the same reduced gradient
+    on every rank.
     """
 
     def __init__(self, model, flat):

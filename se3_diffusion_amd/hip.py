@@ -165,6 +165,24 @@ class FdGroupDwDesc(Structure):
     _fields_ = [("item", FdGroupDwItem * GROUP_DW_MAX_ITEMS), ("nitems", c_int), ("rows", c_long), ("blocks", c_int)]
 
 
+OPT_WS_DOUBLES = 3 * 4096           # include/fd_hip.h FD_OPT_WS_DOUBLES
+OPT_STATE_BYTES = 72                # include/fd_hip.h FD_OPT_STATE_BYTES
+
+
+class FdOptState(Structure):
+    """Host mirror of the DEVICE-resident optimiser state, only to decode the copy optim.FlatAdam.health() makes (the entry
+    points take the state as a device pointer, code "p")."""
+    __slots__ = ()           # (a misspelt field raises instead of becoming a Python attribute)
+    _fields_ = [
+        ("step", c_long), ("skipped", c_long), ("clipped", c_long), ("nonfinite", c_long),
+        ("grad_norm", c_double), ("clip_coef", c_double), ("max_abs", c_double),
+        ("bc1", c_float), ("rsqrt_bc2", c_float), ("coef", c_float), ("apply", c_int),
+    ]
+
+
+assert ctypes.sizeof(FdOptState) == OPT_STATE_BYTES
+
+
 ABI_VERSION = 2          # FD_ABI_VERSION of include/fd_hip.h (bumped whenever a descriptor layout or a signature changes)
 
 
@@ -262,6 +280,8 @@ _SIGS = {
     "fd_sample_record": "ppppp" + "S" + "piili" + "pppp" + "s",
     "fd_dsm_loss": "Ss",
     "fd_adam_step": "pppplffffffs",
+    "fd_grad_stats": "plpps",
+    "fd_adam_step_guarded": "pppplddddd" + "i" + "pp" + "s",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

@@ -6,6 +6,16 @@ parameters, gradients and both moments in four flat fp32 buffers -- every ``p.da
 256-byte offset (16-byte inside an ``adjacent`` group), so the GEMM kernels keep their 16-byte operand paths and the data-parallel all-reduce is one message -- and applies
 the same update rule with one kernel.  ``state_dict`` / ``load_state_dict`` use torch.optim.Adam's layout, so
 checkpoints written by either optimiser load into the other.
+
+Guarded step (opt-in: ``max_grad_norm=`` and / or ``skip_nonfinite=True``): ``step()`` issues ``fd_adam_step_guarded``
+instead -- gradient statistics, the decision and the update as three dependent launches.  The global L2 norm of ``flat_g``,
+the clip coefficient ``min(1, max_grad_norm / (norm + 1e-6))`` (torch's ``clip_grad_norm_``), the count of non-finite
+elements, the decision to skip, the count of applied steps and Adam's bias corrections all live in a small device state:
+``step()`` reads nothing back, every data-parallel rank decides alike (take the step after the gradient all-reduce), and the
+launches can be captured and replayed.  ``p.grad`` keeps the UNCLIPPED gradient -- unlike ``clip_grad_norm_`` the
+coefficient is applied inside the update, not written back.  The norm is taken over the finite elements: with
+``max_grad_norm`` alone (``skip_nonfinite=False``) a non-finite gradient element is not skipped and makes its own
+parameter and moments non-finite (and only those).  ``health()`` returns the counters for a logger.
 """
 from __future__ import annotations
 
@@ -18,8 +28,14 @@ _ALIGN = 64   # elements: 256-byte aligned views
 
 
 class FlatAdam:
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, adjacent=None):
-        """adjacent: groups (tuples) of parameters to lay out back to back without padding, in the given order, at the
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, adjacent=None, max_grad_norm=None,
+                 skip_nonfinite=False):
+        """max_grad_norm: clip the gradient by its global L2 norm (None: no clipping; a value <= 0 is refused -- it would
+        select the guarded step with clipping switched off, which nobody who writes 0 means); skip_nonfinite: leave parameters and
+        moments untouched by a step whose gradient has an inf / NaN element.  Either one selects the guarded step (module
+        docstring); with both at their defaults step() is the single fd_adam_step launch.  self.max_grad_norm, like self.lr,
+        is passed by value at every step() and may be changed between steps (a captured step keeps the captured values).
+        adjacent: groups (tuples) of parameters to lay out back to back without padding, in the given order, at the
         position of the group's first member (ScoreNetwork.flat_layout_groups(): weights that one kernel reads as one
         matrix, e.g. IPA's [linear_b ; down_z]).  The state_dict order stays that of `params`."""
         self.params = [p for p in params if p.requires_grad]
@@ -54,8 +70,38 @@ class FlatAdam:
             view.copy_(p.data)
             p.data = view
             p.grad = self.flat_g[o:o + p.numel()].view_as(p)
-        self.t = 0
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm is not None or self.skip_nonfinite
+        self._max_norm_arg()     # (refuses max_grad_norm <= 0 here, not at the first step)
+        self._t = 0              # steps taken by the unguarded step (property t); the guarded step counts on the device
+        self._ws = self._opt_state = self._stats = None
+        if self.guarded:         # (allocated here, not in step(): a captured step must not allocate)
+            self._ws = torch.empty(hip.OPT_WS_DOUBLES, dtype=torch.float64, device=dev)
+            self._opt_state = torch.zeros(hip.OPT_STATE_BYTES // 8, dtype=torch.int64, device=dev)
         self._dirty = False      # flat_g holds a gradient that step() / all_reduce_mean() already consumed (see rebind)
+
+    @property
+    def t(self):
+        """Steps taken, on the host: the unguarded step's count.  A guarded optimiser counts APPLIED steps on the device and
+        has no host count that could go stale: applied_steps() / set_applied_steps()."""
+        if self.guarded:
+            raise AttributeError("a guarded FlatAdam counts its steps on the device: applied_steps() / set_applied_steps()")
+        return self._t
+
+    @t.setter
+    def t(self, value):
+        if self.guarded:
+            raise AttributeError("a guarded FlatAdam counts its steps on the device: applied_steps() / set_applied_steps()")
+        self._t = int(value)
+
+    def _max_norm_arg(self):
+        """max_norm of fd_adam_step_guarded (its "no clipping" is <= 0) from self.max_grad_norm (None: no clipping)"""
+        if self.max_grad_norm is None:
+            return 0.0
+        if not self.max_grad_norm > 0.0:
+            raise ValueError(f"max_grad_norm must be positive or None (no clipping), not {self.max_grad_norm!r}")
+        return self.max_grad_norm
 
     def rebind(self):
         """Make every p.data / p.grad a view of the flat buffers again.  Anything that replaces them behind the
@@ -111,18 +157,64 @@ class FlatAdam:
     # -- update ------------------------------------------------------------------------------------------------------
     def step(self):
         self.rebind()
-        self.t += 1
         b1, b2 = self.betas
+        if self.guarded:
+            hip.get_lib().call("fd_adam_step_guarded", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.numel,
+                               self.lr, b1, b2, self.eps, self._max_norm_arg(), int(self.skip_nonfinite), self._ws,
+                               self._opt_state)
+            self._dirty = True
+            return
+        self._t += 1
         hip.get_lib().call("fd_adam_step", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.numel,
-                           self.lr, b1, b2, self.eps, 1.0 - b1 ** self.t, 1.0 - b2 ** self.t)
+                           self.lr, b1, b2, self.eps, 1.0 - b1 ** self._t, 1.0 - b2 ** self._t)
         self._dirty = True
+
+    # -- gradient health ---------------------------------------------------------------------------------------------
+    def grad_stats(self, out=None):
+        """fd_grad_stats of the current flat_g: a device tensor of 4 doubles {sum of squares over the finite elements, count of
+        non-finite elements, max |g| over the finite ones, 0}; nothing is read back.  Without `out` the result is ONE tensor
+        owned by the optimiser, allocated at the first call and overwritten by every later one (no allocation or fill per
+        step; call once before capturing, or pass `out`: a contiguous float64 tensor of 4 elements on the buffer's device).
+        In data-parallel training call it after all_reduce_mean() / OverlapAllReduce.finish(), so every rank sees the same
+        figures."""
+        self.rebind()
+        if self._ws is None:
+            self._ws = torch.empty(hip.OPT_WS_DOUBLES, dtype=torch.float64, device=self.flat_g.device)
+        if out is None:
+            if self._stats is None:
+                self._stats = torch.zeros(4, dtype=torch.float64, device=self.flat_g.device)
+            out = self._stats
+        assert out.dtype == torch.float64 and out.numel() == 4 and out.is_contiguous(), "out: 4 contiguous doubles"
+        hip.get_lib().call("fd_grad_stats", self.flat_g, self.numel, self._ws, out)
+        return out
+
+    def health(self):
+        """The guarded step's device state as Python numbers, with ONE device-to-host copy (for a logger that calls it every k
+        steps): step (applied steps), skipped, clipped (counters), and nonfinite, grad_norm, clip_coef, max_abs of the latest
+        step() (grad_norm / max_abs over the finite elements; clip_coef = 1 for a skipped step)."""
+        assert self.guarded, "health() reads the state of the guarded step (max_grad_norm= / skip_nonfinite=)"
+        st = hip.FdOptState.from_buffer_copy(self._opt_state.cpu().numpy().tobytes())
+        return {"step": int(st.step), "skipped": int(st.skipped), "clipped": int(st.clipped), "nonfinite": int(st.nonfinite),
+                "grad_norm": float(st.grad_norm), "clip_coef": float(st.clip_coef), "max_abs": float(st.max_abs)}
+
+    def applied_steps(self):
+        """Adam's t: the device counter when guarded (one device-to-host copy), the host count otherwise."""
+        return self.health()["step"] if self.guarded else self._t
+
+    def set_applied_steps(self, t):
+        """Set Adam's t (what load_state_dict does with a checkpoint's "step"): the device counter when guarded."""
+        if self.guarded:
+            self._opt_state[:1].fill_(int(t))      # (FdOptState.step)
+        else:
+            self._t = int(t)
 
     # -- torch.optim.Adam-compatible checkpoints (data/utils.py:353-362 saves optimizer.state_dict()) ----------------
     def state_dict(self):
         state = {}
+        t = self.applied_steps()
         for i, (p, o) in enumerate(zip(self.params, self.offsets)):
             n = p.numel()
-            state[i] = {"step": torch.tensor(float(self.t)),
+            state[i] = {"step": torch.tensor(float(t)),
                         "exp_avg": self.exp_avg[o:o + n].view_as(p).clone(),
                         "exp_avg_sq": self.exp_avg_sq[o:o + n].view_as(p).clone()}
         group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0, "amsgrad": False,
@@ -134,6 +226,7 @@ class FlatAdam:
         group = sd["param_groups"][0]
         self.lr, self.betas, self.eps = float(group["lr"]), tuple(float(b) for b in group["betas"]), float(group["eps"])
         assert not group.get("weight_decay", 0) and not group.get("amsgrad", False), "plain Adam only"
+        t = None
         for i, (p, o) in enumerate(zip(self.params, self.offsets)):
             st = sd["state"].get(i)
             if st is None:
@@ -141,4 +234,6 @@ class FlatAdam:
             n = p.numel()
             self.exp_avg[o:o + n].copy_(st["exp_avg"].reshape(-1))
             self.exp_avg_sq[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
-            self.t = int(float(st["step"]))
+            t = int(float(st["step"]))
+        if t is not None:        # (a checkpoint without optimiser state leaves the count alone)
+            self.set_applied_steps(t)

@@ -626,6 +626,14 @@ int fd_dsm_loss(const FdLossDesc* desc, void* stream);
 int fd_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
                  float bc1, float bc2, void* stream);
 
+/* fd_adam_step that also carries an exponential moving average of the parameters (the weights a diffusion model is sampled
+ * from; the reference keeps none) in a fifth flat buffer of the same length and alignment: after p is updated,
+ * ema += one_minus_decay * (p - ema) on the same elements, in the same launch (8 more bytes per parameter).
+ * one_minus_decay = (float)(1 - d_t) strictly between 0 and 1, supplied by the host like bc_i (a warm-up schedule of d_t is
+ * the caller's); p, m, v come out bit for bit as from fd_adam_step. */
+int fd_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
+                     float bc1, float bc2, float one_minus_decay, void* stream);
+
 /* ---- gradient health and the guarded optimiser step (se3_diffusion_amd/csrc/fd_optim.hip) ----
  * No reference lines stand behind these two: the reference tests torch.isnan(loss) on the host once per step and aborts
  * (experiments/train_se3_diffusion.py:448-454).  The torch calls they restate are torch.nn.utils.clip_grad_norm_ followed
@@ -635,7 +643,7 @@ int fd_adam_step(float* p, const float* g, float* m, float* v, long n, float lr,
  * bitwise reproducible for a given n.
  *
  * workspace: FD_OPT_WS_DOUBLES doubles of device scratch (per-block partials; launches that may run at the same time need
- * workspaces of their own).  Both entry points follow the empty-input rule: n == 0 returns FD_OK without a launch and
+ * workspaces of their own).  The entry points follow the empty-input rule: n == 0 returns FD_OK without a launch and
  * without touching stats / p / m / v / state. */
 #define FD_OPT_WS_DOUBLES (3 * 4096)
 #define FD_OPT_STATE_BYTES 72
@@ -670,6 +678,16 @@ int fd_grad_stats(const float* g, long n, double* workspace, double* stats, void
  * elements; with skip_nonfinite == 0 a non-finite element therefore reaches its own p, m, v (and only those). */
 int fd_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
                          double max_norm, int skip_nonfinite, double* workspace, void* state, void* stream);
+
+/* fd_adam_step_guarded that also carries the moving average of fd_adam_step_ema: the update launch ends with
+ * ema += a * (p - ema), a = (float)(1 - d_t), d_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay in fp64 on
+ * the device, t = state->step after this call's decision (applied steps, this one included).  apply == 0 touches neither
+ * p, m, v nor ema, so the average never sees a step that was not taken and the warm-up does not advance.  ema_decay strictly
+ * between 0 and 1; the state keeps its layout (nothing of the average lives in it); p, m, v and *state come out bit for bit
+ * as from fd_adam_step_guarded. */
+int fd_adam_step_guarded_ema(float* p, const float* g, float* m, float* v, float* ema, long n, double lr, double b1, double b2,
+                             double eps, double max_norm, int skip_nonfinite, double* workspace, void* state, double ema_decay,
+                             int ema_warmup, void* stream);
 
 #ifdef __cplusplus
 }

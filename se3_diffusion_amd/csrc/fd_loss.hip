@@ -322,11 +322,15 @@ extern "C" int fd_dsm_loss(const FdLossDesc* desc, void* stream_) {
 // The update rule of torch.optim.Adam with its defaults (no weight decay, no amsgrad), as configured by
 // experiments/train_se3_diffusion.py:139 (Adam, lr 1e-4):
 //   m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),  bc_i = 1 - b_i^t
+// EMA = true (fd_adam_step_ema) carries an exponential moving average of the parameters in a fifth flat buffer: E += a (P - E)
+// on the float4 that holds the new P, a = 1 - decay of this step from the host (8 more bytes per parameter; a pass of its own
+// would move 12 and need a launch).  EMA = false is fd_adam_step: `ema` and `a`, the last two arguments, are not read.
 namespace {
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ m, float* __restrict__ v, long n4,
                                                         float lr, float b1, float b2, float eps, float bc1,
-                                                        float rsqrt_bc2) {
+                                                        float rsqrt_bc2, float* __restrict__ ema, float a) {
   const float step = lr / bc1;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
     float4 P = reinterpret_cast<float4*>(p)[i];
@@ -342,7 +346,20 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, c
     reinterpret_cast<float4*>(p)[i] = P;
     reinterpret_cast<float4*>(m)[i] = M;
     reinterpret_cast<float4*>(v)[i] = V;
+    if constexpr (EMA) {
+      float4 E = reinterpret_cast<float4*>(ema)[i];
+      E.x += a * (P.x - E.x);
+      E.y += a * (P.y - E.y);
+      E.z += a * (P.z - E.z);
+      E.w += a * (P.w - E.w);
+      reinterpret_cast<float4*>(ema)[i] = E;
+    }
   }
+}
+
+int adam_grid(long n4) {
+  const long gsz = (n4 + 255) / 256;
+  return (int)(gsz > 4096 ? 4096 : gsz);
 }
 }  // namespace
 
@@ -353,10 +370,24 @@ extern "C" int fd_adam_step(float* p, const float* g, float* m, float* v, long n
                "fd_adam_step: flat buffers must be 16-byte aligned with a length that is a multiple of 4");
   if (n == 0) return FD_OK;
   const long n4 = n / 4;
-  long gsz = (n4 + 255) / 256;
-  const int grid = (int)(gsz > 4096 ? 4096 : gsz);
-  hipLaunchKernelGGL(adam_step_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, lr, b1, b2, eps,
-                     bc1, 1.0f / sqrtf(bc2));
+  float* no_ema = nullptr;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_step_kernel<false>), dim3(adam_grid(n4)), dim3(256), 0, (hipStream_t)stream, p, g, m,
+                     v, n4, lr, b1, b2, eps, bc1, 1.0f / sqrtf(bc2), no_ema, 0.f);
   FD_CHECK_LAUNCH("fd_adam_step");
+  return FD_OK;
+}
+
+extern "C" int fd_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1,
+                                float b2, float eps, float bc1, float bc2, float one_minus_decay, void* stream) {
+  FD_CHECK_ARG(p && g && m && v && ema, "fd_adam_step_ema: null operand");
+  FD_CHECK_ARG((n & 3) == 0 && fd_aligned16(p) && fd_aligned16(g) && fd_aligned16(m) && fd_aligned16(v) && fd_aligned16(ema),
+               "fd_adam_step_ema: flat buffers must be 16-byte aligned with a length that is a multiple of 4");
+  FD_CHECK_ARG(one_minus_decay > 0.f && one_minus_decay < 1.f,
+               "fd_adam_step_ema: one_minus_decay must lie strictly between 0 and 1 (a decay of 0 or 1 is no average)");
+  if (n == 0) return FD_OK;
+  const long n4 = n / 4;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_step_kernel<true>), dim3(adam_grid(n4)), dim3(256), 0, (hipStream_t)stream, p, g, m,
+                     v, n4, lr, b1, b2, eps, bc1, 1.0f / sqrtf(bc2), ema, one_minus_decay);
+  FD_CHECK_LAUNCH("fd_adam_step_ema");
   return FD_OK;
 }

@@ -11,7 +11,7 @@
 //   K2 grad_finalize_kernel  one block: thread t adds the partials t, t + 256, ... in index order, the 256 thread sums go
 //                            through the same fixed shuffle / LDS tree; thread 0 then decides the step in the FdOptState
 //   K3 adam_guarded_kernel   adam_step_kernel's arithmetic (fd_loss.hip) on coef * g, with lr/bc1, 1/sqrt(bc2), coef and
-//                            `apply` read from the state; returns before touching p, m, v when apply == 0
+//                            `apply` read from the state; returns before touching p, m, v (and ema) when apply == 0
 // Every order of additions is a function of (n, grid) alone, and the grid is a function of n.
 #include "fd_common.h"
 #include "../../include/fd_hip.h"
@@ -137,12 +137,27 @@ __global__ __launch_bounds__(OT) void grad_finalize_kernel(const double* __restr
   st->apply = apply;
 }
 
+// EMA = true (fd_adam_step_guarded_ema): E += a (P - E) on the float4 that holds the new P, a = 1 - d_t with
+// d_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay in fp64 from t = st->step, which K2 has advanced for this call.  A
+// skipped call returns before touching ema, and t counts applied steps only.  EMA = false reads none of the last three arguments.
+template <bool EMA>
 __global__ __launch_bounds__(OT) void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v, long n4, float lr,
-                                                          float b1, float b2, float eps, const FdOptState* __restrict__ st) {
+                                                          float b1, float b2, float eps, const FdOptState* __restrict__ st,
+                                                          float* __restrict__ ema, double decay, int warmup) {
   if (st->apply == 0) return;
   const float coef = st->coef, rsqrt_bc2 = st->rsqrt_bc2;
   const float step = lr / st->bc1;
+  float a = 0.f;
+  if constexpr (EMA) {
+    double d = decay;
+    if (warmup) {
+      const double t = (double)st->step;
+      const double w = (1.0 + t) / (10.0 + t);
+      d = w < d ? w : d;
+    }
+    a = (float)(1.0 - d);
+  }
   for (long i = (long)blockIdx.x * OT + threadIdx.x; i < n4; i += (long)gridDim.x * OT) {
     float4 P = reinterpret_cast<float4*>(p)[i];
     const float4 Gd = reinterpret_cast<const float4*>(g)[i];
@@ -160,6 +175,14 @@ __global__ __launch_bounds__(OT) void adam_guarded_kernel(float* __restrict__ p,
     reinterpret_cast<float4*>(p)[i] = P;
     reinterpret_cast<float4*>(m)[i] = M;
     reinterpret_cast<float4*>(v)[i] = V;
+    if constexpr (EMA) {
+      float4 E = reinterpret_cast<float4*>(ema)[i];
+      E.x += a * (P.x - E.x);
+      E.y += a * (P.y - E.y);
+      E.z += a * (P.z - E.z);
+      E.w += a * (P.w - E.w);
+      reinterpret_cast<float4*>(ema)[i] = E;
+    }
   }
 }
 
@@ -189,6 +212,31 @@ extern "C" int fd_grad_stats(const float* g, long n, double* workspace, double* 
   return FD_OK;
 }
 
+namespace {
+
+// the three launches of both guarded entry points (arguments checked by the caller)
+template <bool EMA>
+int guarded_launch(float* p, const float* g, float* m, float* v, float* ema, long n, double lr, double b1, double b2, double eps,
+                   double max_norm, int skip_nonfinite, double* workspace, void* state, double ema_decay, int ema_warmup,
+                   void* stream) {
+  const long n4 = n / 4;
+  const int grid = opt_grid(n4);
+  FdOptState* st = (FdOptState*)state;
+  hipLaunchKernelGGL(grad_stats_kernel, dim3(grid), dim3(OT), 0, (hipStream_t)stream, g, n4, workspace);
+  FD_CHECK_LAUNCH(EMA ? "fd_adam_step_guarded_ema(partials)" : "fd_adam_step_guarded(partials)");
+  const OptDecide cfg = {b1, b2, max_norm, skip_nonfinite};
+  double* no_stats = nullptr;
+  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, (const double*)workspace, grid, no_stats,
+                     st, cfg);
+  FD_CHECK_LAUNCH(EMA ? "fd_adam_step_guarded_ema(decide)" : "fd_adam_step_guarded(decide)");
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_guarded_kernel<EMA>), dim3(grid), dim3(OT), 0, (hipStream_t)stream, p, g, m, v, n4,
+                     (float)lr, (float)b1, (float)b2, (float)eps, (const FdOptState*)st, ema, ema_decay, ema_warmup);
+  FD_CHECK_LAUNCH(EMA ? "fd_adam_step_guarded_ema(update)" : "fd_adam_step_guarded(update)");
+  return FD_OK;
+}
+
+}  // namespace
+
 extern "C" int fd_adam_step_guarded(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2,
                                     double eps, double max_norm, int skip_nonfinite, double* workspace, void* state,
                                     void* stream) {
@@ -199,18 +247,22 @@ extern "C" int fd_adam_step_guarded(float* p, const float* g, float* m, float* v
   FD_CHECK_ARG((((uintptr_t)state) & 7u) == 0 && (((uintptr_t)workspace) & 7u) == 0,
                "fd_adam_step_guarded: workspace and state must be 8-byte aligned");
   if (n == 0) return FD_OK;
-  const long n4 = n / 4;
-  const int grid = opt_grid(n4);
-  FdOptState* st = (FdOptState*)state;
-  hipLaunchKernelGGL(grad_stats_kernel, dim3(grid), dim3(OT), 0, (hipStream_t)stream, g, n4, workspace);
-  FD_CHECK_LAUNCH("fd_adam_step_guarded(partials)");
-  const OptDecide cfg = {b1, b2, max_norm, skip_nonfinite};
-  double* no_stats = nullptr;
-  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(OT), 0, (hipStream_t)stream, (const double*)workspace, grid, no_stats,
-                     st, cfg);
-  FD_CHECK_LAUNCH("fd_adam_step_guarded(decide)");
-  hipLaunchKernelGGL(adam_guarded_kernel, dim3(grid), dim3(OT), 0, (hipStream_t)stream, p, g, m, v, n4, (float)lr, (float)b1,
-                     (float)b2, (float)eps, (const FdOptState*)st);
-  FD_CHECK_LAUNCH("fd_adam_step_guarded(update)");
-  return FD_OK;
+  return guarded_launch<false>(p, g, m, v, nullptr, n, lr, b1, b2, eps, max_norm, skip_nonfinite, workspace, state, 0.0, 0,
+                               stream);
+}
+
+extern "C" int fd_adam_step_guarded_ema(float* p, const float* g, float* m, float* v, float* ema, long n, double lr, double b1,
+                                        double b2, double eps, double max_norm, int skip_nonfinite, double* workspace,
+                                        void* state, double ema_decay, int ema_warmup, void* stream) {
+  FD_CHECK_ARG(p && g && m && v && ema, "fd_adam_step_guarded_ema: null operand");
+  FD_CHECK_ARG(workspace && state, "fd_adam_step_guarded_ema: null workspace or state");
+  FD_CHECK_ARG(n >= 0 && (n & 3) == 0 && fd_aligned16(p) && fd_aligned16(g) && fd_aligned16(m) && fd_aligned16(v) &&
+                   fd_aligned16(ema),
+               "fd_adam_step_guarded_ema: flat buffers must be 16-byte aligned with a length that is a multiple of 4");
+  FD_CHECK_ARG((((uintptr_t)state) & 7u) == 0 && (((uintptr_t)workspace) & 7u) == 0,
+               "fd_adam_step_guarded_ema: workspace and state must be 8-byte aligned");
+  FD_CHECK_ARG(ema_decay > 0.0 && ema_decay < 1.0, "fd_adam_step_guarded_ema: ema_decay must lie strictly between 0 and 1");
+  if (n == 0) return FD_OK;
+  return guarded_launch<true>(p, g, m, v, ema, n, lr, b1, b2, eps, max_norm, skip_nonfinite, workspace, state, ema_decay,
+                              ema_warmup, stream);
 }

@@ -280,8 +280,10 @@ _SIGS = {
     "fd_sample_record": "ppppp" + "S" + "piili" + "pppp" + "s",
     "fd_dsm_loss": "Ss",
     "fd_adam_step": "pppplffffffs",
+    "fd_adam_step_ema": "ppppplfffffffs",
     "fd_grad_stats": "plpps",
     "fd_adam_step_guarded": "pppplddddd" + "i" + "pp" + "s",
+    "fd_adam_step_guarded_ema": "ppppplddddd" + "i" + "pp" + "di" + "s",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

@@ -16,8 +16,21 @@ launches can be captured and replayed.  ``p.grad`` keeps the UNCLIPPED gradient 
 coefficient is applied inside the update, not written back.  The norm is taken over the finite elements: with
 ``max_grad_norm`` alone (``skip_nonfinite=False``) a non-finite gradient element is not skipped and makes its own
 parameter and moments non-finite (and only those).  ``health()`` returns the counters for a logger.
+
+Moving average (opt-in: ``ema_decay=``): a fifth flat buffer ``ema`` holds an exponential moving average of the parameters,
+the weights a diffusion model is sampled and evaluated from.  ``step()`` issues ``fd_adam_step_ema`` /
+``fd_adam_step_guarded_ema`` instead: the same launches, whose update kernel ends with ``E += (1 - d_t) (P - E)`` on the
+parameters it has just written (8 more bytes per parameter, no further launch).  ``d_t = ema_decay``, or with
+``ema_warmup`` ``min(ema_decay, (1 + t) / (10 + t))`` with t the number of applied steps including this one.  A step the
+guard skipped touches the average as little as the parameters, and does not advance the warm-up.  ``ema_weights()`` lets the
+model compute with the average, ``ema_state_dict(model)`` / ``load_ema_state_dict(model, sd)`` carry it in a checkpoint of the
+model's own keys; ``state_dict()`` stays torch.optim.Adam's layout and knows nothing of it.  Data parallel: nothing to add --
+the update is elementwise and deterministic on identical parameters, so ranks that stepped on the same reduced gradient hold
+the same average bit for bit.
 """
 from __future__ import annotations
+
+import contextlib
 
 import torch
 import torch.distributed as dist
@@ -29,7 +42,7 @@ _ALIGN = 64   # elements: 256-byte aligned views
 
 class FlatAdam:
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, adjacent=None, max_grad_norm=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, ema_decay=None, ema_warmup=True):
         """max_grad_norm: clip the gradient by its global L2 norm (None: no clipping; a value <= 0 is refused -- it would
         select the guarded step with clipping switched off, which nobody who writes 0 means); skip_nonfinite: leave parameters and
         moments untouched by a step whose gradient has an inf / NaN element.  Either one selects the guarded step (module
@@ -37,7 +50,12 @@ class FlatAdam:
         is passed by value at every step() and may be changed between steps (a captured step keeps the captured values).
         adjacent: groups (tuples) of parameters to lay out back to back without padding, in the given order, at the
         position of the group's first member (ScoreNetwork.flat_layout_groups(): weights that one kernel reads as one
-        matrix, e.g. IPA's [linear_b ; down_z]).  The state_dict order stays that of `params`."""
+        matrix, e.g. IPA's [linear_b ; down_z]).  The state_dict order stays that of `params`.
+        ema_decay: keep a moving average of the parameters in self.ema (module docstring); None (default) allocates nothing and
+        leaves step() the launches it has without it; a value outside (0, 1) is refused.  Like self.lr it is passed by value
+        at every step() and may be changed between steps (not to None or from None: the buffer is allocated here).
+        ema_warmup: d_t = min(ema_decay, (1 + t) / (10 + t)), so that the first steps do not average in the initial weights
+        with the full decay."""
         self.params = [p for p in params if p.requires_grad]
         assert self.params, "no trainable parameters"
         assert all(p.dtype == torch.float32 for p in self.params), "fp32 parameters only"
@@ -80,6 +98,13 @@ class FlatAdam:
             self._ws = torch.empty(hip.OPT_WS_DOUBLES, dtype=torch.float64, device=dev)
             self._opt_state = torch.zeros(hip.OPT_STATE_BYTES // 8, dtype=torch.int64, device=dev)
         self._dirty = False      # flat_g holds a gradient that step() / all_reduce_mean() already consumed (see rebind)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = None
+        self._ema_live = False   # inside ema_weights(): flat_p holds the average, ema the training weights
+        if self.ema_decay is not None:
+            self._ema_decay_arg()                # (refuses a decay outside (0, 1) here, not at the first step)
+            self.ema = self.flat_p.clone()       # (padding between the views is zero in both and stays zero)
 
     @property
     def t(self):
@@ -102,6 +127,11 @@ class FlatAdam:
         if not self.max_grad_norm > 0.0:
             raise ValueError(f"max_grad_norm must be positive or None (no clipping), not {self.max_grad_norm!r}")
         return self.max_grad_norm
+
+    def _ema_decay_arg(self):
+        if not 0.0 < self.ema_decay < 1.0:
+            raise ValueError(f"ema_decay must lie strictly between 0 and 1 (or be None: no average), not {self.ema_decay!r}")
+        return self.ema_decay
 
     def rebind(self):
         """Make every p.data / p.grad a view of the flat buffers again.  Anything that replaces them behind the
@@ -156,18 +186,112 @@ class FlatAdam:
 
     # -- update ------------------------------------------------------------------------------------------------------
     def step(self):
+        if self._ema_live:
+            raise RuntimeError("step() inside ema_weights(): the parameters are the average there, not the training weights")
         self.rebind()
         b1, b2 = self.betas
         if self.guarded:
-            hip.get_lib().call("fd_adam_step_guarded", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.numel,
-                               self.lr, b1, b2, self.eps, self._max_norm_arg(), int(self.skip_nonfinite), self._ws,
-                               self._opt_state)
+            if self.ema is None:
+                hip.get_lib().call("fd_adam_step_guarded", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.numel,
+                                   self.lr, b1, b2, self.eps, self._max_norm_arg(), int(self.skip_nonfinite), self._ws,
+                                   self._opt_state)
+            else:
+                hip.get_lib().call("fd_adam_step_guarded_ema", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.ema,
+                                   self.numel, self.lr, b1, b2, self.eps, self._max_norm_arg(), int(self.skip_nonfinite),
+                                   self._ws, self._opt_state, self._ema_decay_arg(), int(self.ema_warmup))
             self._dirty = True
             return
-        self._t += 1
-        hip.get_lib().call("fd_adam_step", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.numel,
-                           self.lr, b1, b2, self.eps, 1.0 - b1 ** self._t, 1.0 - b2 ** self._t)
+        if self.ema is None:
+            self._t += 1
+            hip.get_lib().call("fd_adam_step", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.numel,
+                               self.lr, b1, b2, self.eps, 1.0 - b1 ** self._t, 1.0 - b2 ** self._t)
+        else:
+            d = self._ema_decay_arg()            # (before the count advances: a refused decay takes no step)
+            self._t += 1
+            if self.ema_warmup:
+                d = min(d, (1.0 + self._t) / (10.0 + self._t))
+            hip.get_lib().call("fd_adam_step_ema", self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.ema, self.numel,
+                               self.lr, b1, b2, self.eps, 1.0 - b1 ** self._t, 1.0 - b2 ** self._t, 1.0 - d)
         self._dirty = True
+
+    # -- the moving average ------------------------------------------------------------------------------------------
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError("this FlatAdam keeps no moving average (ema_decay=None)")
+
+    def _exchange_ema(self):
+        tmp = self.flat_p.clone()
+        self.flat_p.copy_(self.ema)
+        self.ema.copy_(tmp)
+
+    def reset_ema(self):
+        """Average := the current parameters (after the model loaded a checkpoint that carries no average)."""
+        self._need_ema()
+        if self._ema_live:
+            raise RuntimeError("reset_ema() inside ema_weights()")
+        self.rebind()
+        self.ema.copy_(self.flat_p)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model computes with the averaged weights; after it the training weights are back bit for
+        bit, also when the body raises.  The CONTENTS of flat_p and ema are exchanged in place (copies through one temporary
+        of the flat size), so every p.data stays a view of flat_p at its address and nothing that holds a parameter's address
+        goes stale (dist.FlatGrads, a captured graph, the plane split of the weights, which is keyed by address).  step() and
+        reset_ema() raise inside it, and it does not nest.
+        Do NOT enter it between a training forward and its backward: the backward would read weights (and planes split from
+        them) that are no longer the ones the forward used.  The training forward re-splits the weight planes at every step
+        and a no-grad forward clears them, so the exchange is safe between steps and around sampling."""
+        self._need_ema()
+        if self._ema_live:
+            raise RuntimeError("ema_weights() does not nest")
+        self.rebind()
+        self._exchange_ema()
+        self._ema_live = True
+        try:
+            yield self
+        finally:
+            self._exchange_ema()
+            self._ema_live = False
+
+    def _ema_slices(self, model):
+        """(key, view of self.ema) for every tensor of model.state_dict() that lives inside flat_p, found by address"""
+        self.rebind()
+        at = {self.flat_p.data_ptr() + 4 * o: (o, p.numel()) for p, o in zip(self.params, self.offsets)}
+        out = []
+        for k, t in model.state_dict().items():
+            hit = at.get(t.data_ptr()) if t.dtype == torch.float32 and t.device == self.flat_p.device else None
+            if hit is not None and hit[1] == t.numel():
+                out.append((k, self.ema[hit[0]:hit[0] + hit[1]].view(t.shape)))
+        return out
+
+    def ema_state_dict(self, model):
+        """model.state_dict() with every tensor that lives inside flat_p replaced by a clone of its slice of the average
+        (buffers and frozen parameters are the model's own): the model's keys and shapes, so it loads with strict=True into a
+        ScoreNetwork and into the reference's model -- the "model" entry of a second checkpoint for an unchanged inference
+        script."""
+        self._need_ema()
+        if self._ema_live:
+            raise RuntimeError("ema_state_dict() inside ema_weights(): model.state_dict() is the average there")
+        sd = model.state_dict()
+        for k, view in self._ema_slices(model):
+            sd[k] = view.clone()
+        return sd
+
+    def load_ema_state_dict(self, model, sd):
+        """The inverse of ema_state_dict: the average := the entries of sd that belong to tensors inside flat_p.  A missing
+        key or a wrong shape is an error, and nothing is written then."""
+        self._need_ema()
+        if self._ema_live:
+            raise RuntimeError("load_ema_state_dict() inside ema_weights()")
+        slices = self._ema_slices(model)
+        for k, view in slices:
+            if k not in sd:
+                raise KeyError(f"load_ema_state_dict: missing key {k!r}")
+            if tuple(sd[k].shape) != tuple(view.shape):
+                raise ValueError(f"load_ema_state_dict: {k!r} has shape {tuple(sd[k].shape)}, the model's is {tuple(view.shape)}")
+        for k, view in slices:
+            view.copy_(sd[k])
 
     # -- gradient health ---------------------------------------------------------------------------------------------
     def grad_stats(self, out=None):

@@ -689,6 +689,53 @@ int fd_adam_step_guarded_ema(float* p, const float* g, float* m, float* v, float
                              double eps, double max_norm, int skip_nonfinite, double* workspace, void* state, double ema_decay,
                              int ema_warmup, void* stream);
 
+/* ---- scoring sampled backbones (se3_diffusion_amd/csrc/fd_metrics.hip) ----
+ * The coordinate arithmetic of the reference's sample evaluation (Experiment.eval_fn -> analysis/metrics.py::protein_metrics),
+ * left on the device as fp64: one launch per call, no floating-point atomics, every sum in a fixed order (bitwise
+ * reproducible for a given shape).  The empty-input rule holds: B == 0, P == 0 or N == 0 returns FD_OK without a launch and
+ * writes nothing.  N <= 4096.
+ *
+ * The backbone figures, one block per backbone.  Residue r of backbone b starts at atoms + (b N + r) atom_stride floats and holds
+ * N, CA, C, CB, O in slots 0..4 (three floats each): atom_stride = 111 for atom37 [B,N,37,3], 15 for [B,N,5,3]; below 15 it is
+ * refused.  A residue is present iff res_mask[b,r] != 0; the present residues are compacted in index order, as the reference
+ * does by boolean indexing (analysis/metrics.py:94-95), and rows that are not present are never read into a result.  With n
+ * present residues, out[b][0..12) =
+ *   0 num_res                  n
+ *   1 ca_ca_bond_dev           mean over the n-1 consecutive compacted pairs of |d - 3.80209737096|   (metrics.py:120-125)
+ *   2 ca_ca_valid_percent      mean of (d < 3.80209737096 + 0.1) on the same pairs                     (metrics.py:120-125)
+ *   3 num_ca_steric_clashes    number of compacted pairs i < j with 0 < D_ij < 1.5                     (metrics.py:127-132)
+ *   4 ca_steric_clash_percent  slot 3 / number of pairs i < j with D_ij > 0                            (metrics.py:127-132)
+ *   5 ca_radius_of_gyration    sqrt(mean |ca - mean ca|^2) over the present CA atoms, in Angstrom (NOT mdtraj's figure of
+ *                              metrics.py:62, which takes all atoms and reports nm)
+ *   6 c_n_bond_dev             mean over the same consecutive pairs of | |C_i - N_{i+1}| - 1.329 |
+ *   7 c_n_bond_valid_percent   mean of (| |C_i - N_{i+1}| - 1.329 | <= 12 * 0.014): openfold's non-proline peptide bond
+ *                              length and standard deviation at its tolerance factor 12 (residue_constants.py:546-547)
+ *   8 max_ca_ca_dist           max of the consecutive CA-CA distances (0 if there is none)
+ *   9..11                      0
+ * A mean over an empty set is NaN (as np.mean gives): n < 2 gives NaN in slots 1, 2, 4, 6, 7, n == 0 in slot 5 as well. */
+int fd_backbone_metrics(const float* atoms, long atom_stride, const float* res_mask, int B, int N, double* out, void* stream);
+
+/* Optimal superposition of P pairs of point sets, one block per pair (analysis/metrics.py:71-73 calc_aligned_rmsd on
+ * data/utils.py:519-568 rigid_transform_3D).  Point k of set s starts at A + (s N + k) a_stride floats (B likewise, with
+ * b_stride): a stride of 111 on a pointer to the CA slot reads the CA column of atom37 in place.  Pair p superposes set ia[p] of
+ * A onto set ib[p] of B (ia == ib == NULL: set p of both).  mask (optional, [*,N], indexed like the sets): position k counts iff
+ * it is non-zero in both sets.  The rotation is the optimal PROPER one -- what rigid_transform_3D returns after its reflection
+ * fix -- from the largest eigenvector of Horn's symmetric 4x4 matrix of the fp64 cross-covariance (cyclic Jacobi).  With
+ * d_k = |R a_k + t - b_k| over the L counted positions, out[p][0..8) =
+ *   0 L
+ *   1 mean_dist    mean d_k: what calc_aligned_rmsd returns (a mean of norms, not a root mean square; quirk and name kept)
+ *   2 rmsd         sqrt(mean d_k^2)
+ *   3 tm_kabsch    (1/L) sum 1 / (1 + (d_k/d0)^2), d0 = 1.24 cbrt(L - 15) - 1.8 for L > 21, else 0.5: the TM-score formula
+ *                  under THIS one superposition, a lower bound of the TM-score of the given correspondence (not TM-align's value)
+ *   4 reflection   1.0 iff det(covariance) < 0: rigid_transform_3D's reflection_detected
+ *   5 max_dist     max d_k
+ *   6, 7           0
+ * L == 0 gives NaN in slots 1, 2, 3, 5.  transform (optional): [P][12] = R row-major, then t, with aligned = R a + t as in the
+ * reference's return value.  With fewer than three non-collinear points the distances are those of an optimal superposition
+ * and R is unspecified. */
+int fd_aligned_rmsd(const float* A, long a_stride, const float* B, long b_stride, const int* ia, const int* ib,
+                    const float* mask, int P, int N, double* out, double* transform, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -284,6 +284,8 @@ _SIGS = {
     "fd_grad_stats": "plpps",
     "fd_adam_step_guarded": "pppplddddd" + "i" + "pp" + "s",
     "fd_adam_step_guarded_ema": "ppppplddddd" + "i" + "pp" + "di" + "s",
+    "fd_backbone_metrics": "plpiips",
+    "fd_aligned_rmsd": "plplpppiipps",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

@@ -1,0 +1,157 @@
+"""Scoring sampled backbones on the device: the coordinate arithmetic of the reference's sample evaluation
+(Experiment.eval_fn -> analysis/metrics.py::protein_metrics) on the kernels of csrc/fd_metrics.hip.
+
+From the reference: ca_ca_distance (analysis/metrics.py:120-125), ca_ca_clashes (:127-132) and calc_aligned_rmsd (:71-73) on
+data/utils.py::rigid_transform_3D (:519-568) -- the columns ca_ca_bond_dev, ca_ca_valid_percent, num_ca_steric_clashes and
+ca_steric_clash_percent of its metrics.csv, and the superposition of its self-consistency step.  This module's own: a peptide-bond
+(C-N) check, a CA radius of gyration (in Angstrom over the CA atoms: NOT mdtraj's radius_of_gyration column, which takes all atoms
+and reports nm), and tm_kabsch, the TM-score formula under the one least-squares superposition -- a lower bound of the TM-score
+of the given correspondence, not TM-align's value.  Not here: the DSSP fractions, mdtraj's Rg, the OpenMM
+violation losses and TM-align.
+
+Every value stays on the device as float64; only eval_rows copies to the host, once.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import hip
+
+BACKBONE_SLOTS = ("num_res", "ca_ca_bond_dev", "ca_ca_valid_percent", "num_ca_steric_clashes", "ca_steric_clash_percent",
+                  "ca_radius_of_gyration", "c_n_bond_dev", "c_n_bond_valid_percent", "max_ca_ca_dist")
+RMSD_SLOTS = ("num_aligned", "mean_dist", "rmsd", "tm_kabsch", "reflection", "max_dist")
+CA = 1                   # slot of CA in atom37 / the compact [.,5,3] order N, CA, C, CB, O
+
+
+def _f32c(x):
+    return x if x.dtype == torch.float32 and x.is_contiguous() else x.to(torch.float32).contiguous()
+
+
+def _backbone_block(atoms, res_mask=None, out=None):
+    """[B,12] float64: fd_backbone_metrics' rows for atoms [B,N,A,3] (A = 37 or 5), one launch."""
+    if atoms.dim() != 4 or atoms.shape[-1] != 3 or atoms.shape[-2] not in (5, 37):
+        raise ValueError(f"atoms of shape {tuple(atoms.shape)}: expected [B,N,37,3] or [B,N,5,3] (or the same without B)")
+    B, N, A = atoms.shape[:3]
+    atoms = _f32c(atoms)
+    if res_mask is None:
+        # the reference's own mask (analysis/metrics.py:86,94): a residue is present iff any of its coordinates is non-zero
+        res_mask = (atoms != 0).reshape(B, N, A * 3).any(-1)
+    res_mask = _f32c(res_mask.reshape(B, N))
+    if out is None:
+        out = torch.empty((B, 12), dtype=torch.float64, device=atoms.device)
+    elif out.shape != (B, 12) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError(f"out: expected a contiguous float64 [{B},12] tensor")
+    hip.get_lib().call("fd_backbone_metrics", atoms, A * 3, res_mask, B, N, out)
+    return out
+
+
+def backbone_metrics(atoms, res_mask=None, out=None):
+    """Per-backbone geometry of atoms [B,N,37,3] or [B,N,5,3] (atom order N, CA, C, CB, O; or the same without B):
+    dict name -> float64 device tensor [B] (0-d without B) under BACKBONE_SLOTS, the slot table of include/fd_hip.h.  res_mask [B,N]:
+    a residue is present iff its value is non-zero; None derives it the reference's way (present iff any coordinate is non-zero).
+    out: a float64 [B,12] tensor to write (the returned tensors are views of it).  One launch, no host synchronisation."""
+    batched = atoms.dim() == 4
+    if not batched:
+        atoms = atoms[None]
+        res_mask = None if res_mask is None else res_mask[None]
+    blk = _backbone_block(atoms, res_mask, out)
+    return {name: (blk[:, k] if batched else blk[0, k]) for k, name in enumerate(BACKBONE_SLOTS)}
+
+
+def _points(pos):
+    """fp32 [P,N,3] whose layout fd_aligned_rmsd can address in place: unit stride along xyz, one point stride, sets N points apart"""
+    if pos.dim() != 3 or pos.shape[-1] != 3:
+        raise ValueError(f"points of shape {tuple(pos.shape)}: expected [P,N,3] or [N,3]")
+    P, N = pos.shape[:2]
+    ok = pos.dtype == torch.float32 and pos.stride(2) == 1 and pos.stride(1) >= 3 and (P == 1 or pos.stride(0) == N * pos.stride(1))
+    if not ok:
+        pos = pos.to(torch.float32).contiguous()
+    return pos, (pos.stride(1) if N > 1 else 3)
+
+
+def _rmsd_call(pos_1, pos_2, mask, ia, ib, P, want_transform):
+    a, a_stride = _points(pos_1)
+    b, b_stride = _points(pos_2)
+    N = a.shape[1]
+    dev = a.device
+    if mask is not None:
+        mask = _f32c(mask.reshape(-1, N))
+    out = torch.empty((P, 8), dtype=torch.float64, device=dev)
+    tr = torch.empty((P, 12), dtype=torch.float64, device=dev) if want_transform else None
+    hip.get_lib().call("fd_aligned_rmsd", a, a_stride, b, b_stride, ia, ib, mask, P, N, out, tr)
+    return out, tr
+
+
+def aligned_rmsd(pos_1, pos_2, mask=None, return_transform=False):
+    """Least-squares superposition of pos_1 onto pos_2 ([P,N,3] or [N,3]; a strided view such as atom37[:, :, 1] is read in
+    place) by the optimal proper rotation, rigid_transform_3D's after its reflection fix.  mask [P,N] (or [N]): the positions that
+    count.  dict name -> float64 device tensor [P] (0-d without P) under RMSD_SLOTS: mean_dist is the reference's
+    calc_aligned_rmsd (a mean of distances, not a root mean square), rmsd the root mean square, tm_kabsch the TM-score formula
+    under this superposition, reflection 1.0 iff the reference would report reflection_detected.  return_transform adds R [P,3,3] and
+    t [P,3] with aligned = R a + t.  One launch, no host synchronisation."""
+    batched = pos_1.dim() == 3
+    if not batched:
+        pos_1, pos_2 = pos_1[None], pos_2[None]
+    if pos_1.shape != pos_2.shape:
+        raise ValueError(f"point sets of shapes {tuple(pos_1.shape)} and {tuple(pos_2.shape)}")
+    P = pos_1.shape[0]
+    out, tr = _rmsd_call(pos_1, pos_2, mask, None, None, P, return_transform)
+    pick = (lambda x: x) if batched else (lambda x: x[0])
+    res = {name: pick(out[:, k]) for k, name in enumerate(RMSD_SLOTS)}
+    if return_transform:
+        res["R"] = pick(tr[:, :9].reshape(P, 3, 3))
+        res["t"] = pick(tr[:, 9:])
+    return res
+
+
+def pairwise_rmsd(pos, mask=None):
+    """All-pairs superposed distances of M point sets pos [M,N,3] (mask [M,N]: a position counts in a pair iff it is non-zero in
+    both sets): dict of float64 [M,M] device tensors mean_dist, rmsd, tm_kabsch -- the quantity sample diversity is computed
+    from.  One launch over the M (M - 1) / 2 upper pairs; the result is mirrored, the diagonal is 0, 0 and 1."""
+    if pos.dim() != 3:
+        raise ValueError(f"points of shape {tuple(pos.shape)}: expected [M,N,3]")
+    M = pos.shape[0]
+    dev = pos.device
+    iu = torch.triu_indices(M, M, 1, device=dev)
+    ia, ib = iu[0].to(torch.int32).contiguous(), iu[1].to(torch.int32).contiguous()
+    P = ia.numel()
+    out, _ = _rmsd_call(pos, pos, mask, ia, ib, P, False)
+    res = {}
+    for name, diag in (("mean_dist", 0.0), ("rmsd", 0.0), ("tm_kabsch", 1.0)):
+        m = torch.zeros((M, M), dtype=torch.float64, device=dev)
+        v = out[:, RMSD_SLOTS.index(name)]
+        m[iu[0], iu[1]] = v
+        m[iu[1], iu[0]] = v
+        m.fill_diagonal_(diag)
+        res[name] = m
+    return res
+
+
+def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None):
+    """One dict of Python floats per backbone with the reference's column names (Experiment.eval_fn,
+    experiments/train_se3_diffusion.py:475-508, and CA_VIOLATION_METRICS): ca_ca_bond_dev, ca_ca_valid_percent,
+    ca_steric_clash_percent, num_ca_steric_clashes, num_res, fixed_residues, diffused_percentage -- and this module's own
+    BACKBONE_SLOTS.  gt_atom37 adds aligned_rmsd_to_gt (calc_aligned_rmsd of the sample's CA onto the ground truth's) over the
+    diffused present residues (analysis/metrics.py:100-102).  One device-to-host copy."""
+    B, N = atom37.shape[:2]
+    res_mask = res_mask.reshape(B, N).to(torch.float32)
+    fixed = torch.zeros_like(res_mask) if fixed_mask is None else fixed_mask.reshape(B, N).to(torch.float32)
+    present = (res_mask != 0).to(torch.float64)
+    cols = [_backbone_block(atom37, res_mask), (fixed.to(torch.float64) * present).sum(-1, keepdim=True)]
+    if gt_atom37 is not None:
+        a37, g37 = _f32c(atom37), _f32c(gt_atom37)
+        diffused = (1.0 - fixed) * (res_mask != 0)
+        out, _ = _rmsd_call(a37[:, :, CA], g37[:, :, CA], diffused, None, None, B, False)
+        cols.append(out)
+    host = torch.cat(cols, dim=1).cpu()
+    rows = []
+    for b in range(B):
+        v = host[b].tolist()
+        row = dict(zip(BACKBONE_SLOTS, v[:len(BACKBONE_SLOTS)]))
+        n = row["num_res"]
+        row["fixed_residues"] = v[12]
+        row["diffused_percentage"] = (n - v[12]) / n if n else float("nan")
+        if gt_atom37 is not None:
+            row["aligned_rmsd_to_gt"] = v[13 + RMSD_SLOTS.index("mean_dist")]
+        rows.append(row)
+    return rows

@@ -36,7 +36,7 @@ def _f64(x, dev):
 
 @torch.no_grad()
 def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_condition=True, center=True,
-           generator=None, noise_fn=None, return_traj=False, use_graph=False, stats=None, record=None):
+           generator=None, noise_fn=None, return_traj=False, use_graph=False, stats=None, record=None, metrics=False):
     """Run the reverse process on `feats` (from init_feats).  noise_fn(step, shape) -> (z_rot, z_trans) injects
     draws (e.g. the numpy stream, for trajectory parity); default draws on the device.
     Returns dict(rigids [B,N,7], atom37 [B,N,37,3], psi, (return_traj: rigid_traj, a list of per-step frames)).  `stats` (a dict)
@@ -54,7 +54,11 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
     final structure, like the reference's flipped arrays) and psi_pred [1,B,N,2].  record="prot": prot_traj only (aux_traj=False).
     Two reference quirks are kept: the final step (t == min_t, :778-780) refreshes neither rigid_pred nor the masks, so
     trans_traj[0] and the frames of rigid_0_traj[0] come from the previous step's prediction while psi is the fresh one; padded
-    rows (res_mask == 0) get zeros in trans_traj but real atoms in prot_traj."""
+    rows (res_mask == 0) get zeros in trans_traj but real atoms in prot_traj.
+
+    metrics=True: the result gains metrics = metrics.backbone_metrics(atom37, res_mask), float64 device tensors [B] per name (CA
+    geometry, clashes, peptide bonds, radius of gyration) from ONE launch issued after the loop, outside the captured step; the
+    steps themselves launch what they launch without it."""
     if record not in (None, "reference", "prot"):
         raise ValueError(f"record={record!r}: expected None, 'reference' or 'prot'")
     if record == "reference" and return_traj:
@@ -262,6 +266,9 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
         if rec["aux"]:
             res.update(rigid_traj=rec["rigid_traj"], trans_traj=rec["trans_0"], rigid_0_traj=_atom37_of(rec["bb_0"]),
                        psi_pred=psi[None])
+    if metrics:
+        from . import metrics as _metrics
+        res["metrics"] = _metrics.backbone_metrics(atom37, st["res_mask"])
     return res
 
 

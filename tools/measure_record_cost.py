@@ -7,6 +7,7 @@ events), full-depth model, use_graph=True.  Run the modes in alternation on one 
     python tools/measure_record_cost.py --mode none        --N 128 --B 1      # no trajectory
     python tools/measure_record_cost.py --mode reference   --N 128 --B 1      # record="reference" (fd_sample_record)
     python tools/measure_record_cost.py --mode inference   --N 128 --B 1      # wall time of a whole inference_fn(aux_traj=True) call
+    python tools/measure_record_cost.py --mode metrics     --N 128 --B 1      # metrics=True (fd_backbone_metrics after the loop)
 
 --root points at another checkout of this project (e.g. the parent commit, built) to measure that tree instead.
 """
@@ -20,7 +21,7 @@ import types
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("return_traj", "none", "reference", "prot", "inference"), required=True)
+    ap.add_argument("--mode", choices=("return_traj", "none", "reference", "prot", "inference", "metrics"), required=True)
     ap.add_argument("--N", type=int, default=128)
     ap.add_argument("--B", type=int, default=1)
     ap.add_argument("--num-t", type=int, default=100)
@@ -41,7 +42,8 @@ def main():
     diff = se3_diffuser.SE3Diffuser(dconf)
     torch.manual_seed(0)
     model = ScoreNetwork(ts.base_model_conf(4), diff).to(dev).eval()
-    kw = {"return_traj": dict(return_traj=True), "none": {}, "reference": dict(record="reference"), "prot": dict(record="prot")}
+    kw = {"return_traj": dict(return_traj=True), "none": {}, "reference": dict(record="reference"), "prot": dict(record="prot"),
+          "metrics": dict(metrics=True)}
     loop, wall = [], []
     for rep in range(a.repeats + 1):            # (the first run pays allocator growth and lazily built tables: not reported)
         gen = torch.Generator(device=dev).manual_seed(1 + rep)

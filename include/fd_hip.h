@@ -736,6 +736,48 @@ int fd_backbone_metrics(const float* atoms, long atom_stride, const float* res_m
 int fd_aligned_rmsd(const float* A, long a_stride, const float* B, long b_stride, const int* ia, const int* ib,
                     const float* mask, int P, int N, double* out, double* transform, void* stream);
 
+/* The TM-score of P pairs under their GIVEN residue-to-residue correspondence, by the superposition search of Zhang & Skolnick's
+ * TM-score program: the tm_score column of the reference's EVAL_METRICS (analysis/metrics.py:44-46,104-105) for pairs whose
+ * correspondence is fixed -- sample against ground truth, against its refolded self, against another sample of equal length.
+ * NOT TM-align: the reference calls tmtools.tm_align, which also searches over alignments; that search is not here, and agreement
+ * with the printed values of tmtools or of the TM-score program has not been verified (neither is available to this project's
+ * tests; they check a float64 restatement of the search below).  Operands as fd_aligned_rmsd (strided points read in place,
+ * ia / ib together or not at all, mask rows indexed like the sets, 8-byte aligned fp64 operands, P == 0 or N == 0 returns FD_OK
+ * without a launch); N <= 2048, seed_step >= 1, max_iter >= 0, parts >= 1 and a non-null ws, or the call is refused.
+ *
+ * The search.  The counting positions (mask non-zero in both sets; all without a mask) are compacted in index order; L is their
+ * number, d0 = 1.24 cbrt(L - 15) - 1.8 for L > 21, else 0.5, and d0s = min(max(d0, 4.5), 8).  All arithmetic after the fp32 loads
+ * is fp64.  Fragment lengths: L, L >> 1, L >> 2, ... while above 4 (at most six), then 4.  Seeds: for each length in that order
+ * the starts 0, seed_step, 2 seed_step, ... <= L - length, numbered from 0; seed 0 is the whole set.
+ *   score(R, t, dcut): d2_k = |R a_k + t - b_k|^2; s = (1/L) sum_k 1 / (1 + d2_k / d0^2); selection = {k: d2_k < dcut^2}; while
+ *                      fewer than 3 positions are selected, dcut += 0.5 and select again (given up after 4096 increments, which
+ *                      only absurd coordinates reach; not attempted when s is not finite -- a NaN or infinite coordinate
+ *                      among the counting positions -- since such a call can never be the result).
+ *   per seed:          superpose the fragment (optimal proper rotation of the centred selected positions, Horn's quaternion as in
+ *                      fd_aligned_rmsd); score(R, t, d0s - 1); then up to max_iter times: superpose the current selection,
+ *                      score(R, t, d0s + 1), stop when the new selection equals the old one.
+ * Every call of score is a candidate; the result is the candidate of the greatest s -- on ties the earliest within a seed and the
+ * lowest seed number.  One wave owns one seed at a time (grid of P * parts blocks of four waves: wave w of part c of a pair takes
+ * the seeds 4 c + w, + 4 parts, ...); the arithmetic of a seed does not depend on which wave ran it, each wave leaves one partial
+ * in ws, and a second small launch reduces them in a fixed order: no floating-point atomics, results bitwise reproducible and
+ * bitwise independent of parts.
+ *   ws: caller-provided scratch of P * parts * 64 doubles (FD_TM_WS_DOUBLES), need not be initialised.
+ * out[p][0..8) =
+ *   0 num_aligned  L
+ *   1 tm_score     the greatest s found (the TM-score of the given correspondence, normalised by L)
+ *   2 tm_kabsch    the first s of seed 0: the formula under the one least-squares superposition (fd_aligned_rmsd's slot 3)
+ *   3 best_seed    number of the seed that found slot 1
+ *   4 num_seeds    seeds searched
+ *   5 d0
+ *   6 passes       calls of score over all seeds: an exact integer, the cost unit of a pair
+ *   7              0
+ * L == 0: slots 1, 2 NaN, best_seed -1, num_seeds 0, passes 0.  1 <= L <= 3: no search -- tm_score = tm_kabsch under the
+ * whole-set superposition, best_seed -1, num_seeds 0, passes 0.  transform (optional): [P][12] = R row-major, then t, of the
+ * superposition that gave slot 1, with aligned = R a + t. */
+#define FD_TM_WS_DOUBLES(P, parts) ((long)(P) * (long)(parts) * 64L)
+int fd_tm_search(const float* A, long a_stride, const float* B, long b_stride, const int* ia, const int* ib, const float* mask,
+                 int P, int N, int seed_step, int max_iter, int parts, double* ws, double* out, double* transform, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

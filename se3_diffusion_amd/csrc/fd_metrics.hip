@@ -1,4 +1,4 @@
-// fd_backbone_metrics / fd_aligned_rmsd: the coordinate arithmetic of the reference's sample evaluation on the device
+// fd_backbone_metrics / fd_aligned_rmsd / fd_tm_search: the coordinate arithmetic of the reference's sample evaluation on the device
 // (analysis/metrics.py:120-125 ca_ca_distance, :127-132 ca_ca_clashes, :71-73 calc_aligned_rmsd on
 // data/utils.py:519-568 rigid_transform_3D), one launch each, the values left in HBM as fp64.
 //
@@ -12,10 +12,19 @@
 // fd_aligned_rmsd      one block per pair: centroids, then the 3x3 cross-covariance, then one thread solves Horn's quaternion
 //                      eigenproblem (largest eigenvector of a symmetric 4x4, cyclic Jacobi) for the optimal PROPER rotation --
 //                      what rigid_transform_3D returns after its reflection fix -- then all threads take the residual distances.
+// fd_tm_search        the TM-score of a given correspondence as the maximum over superpositions, by the seed-and-refine search
+//                      of the TM-score program (include/fd_hip.h spells it out).  parts blocks per pair; each compacts the
+//                      pair's counting positions into LDS once (six fp32 arrays, the prefix scan of fd_backbone_metrics), then
+//                      ONE WAVE owns one seed at a time: lanes stride over the positions, the selection is a per-lane bit mask,
+//                      and every lane solves the 4x4 eigenproblem redundantly from wave sums that are the same bits in all
+//                      lanes.  Seeds take different numbers of refinements, so after the staging there is no block barrier,
+//                      only wave collectives.  Each wave leaves one partial in a caller-provided workspace; a second launch,
+//                      one wave per pair, takes the maximum (lowest seed on ties) and the integer sum of the pass counts.
 //
-// All arithmetic after the fp32 loads is fp64.  No floating-point atomics: every sum is a per-thread run in index order, a
-// butterfly in the wave, then the four wave results in wave order through LDS (fd_optim.hip::block_reduce3's pattern), so the
-// results are bitwise reproducible for a given shape.
+// All arithmetic after the fp32 loads is fp64.  No floating-point atomics: every sum is a per-thread run in index order and a
+// butterfly in the wave; the block-wide sums of the first two entry points then add the four wave results in wave order
+// through LDS (fd_optim.hip::block_reduce3's pattern), the search keeps its sums inside the wave.  The results are bitwise
+// reproducible for a given shape, the search's also whatever parts is.
 #include "fd_common.h"
 #include "../../include/fd_hip.h"
 
@@ -383,6 +392,331 @@ __global__ __launch_bounds__(MT) void aligned_rmsd_kernel(const float* __restric
   }
 }
 
+// ---- fd_tm_search: the TM-score of a fixed correspondence by superposition search -----------------------------------------------
+constexpr int TM_MAX_N = 2048;                    // 6 fp32 arrays of 2048 = 48 KB static LDS
+constexpr int TM_MAX_WIDEN = 4096;                // cutoff increments of 0.5 A before a selection of < 3 positions is accepted
+constexpr int TM_PART = 16;                       // doubles per wave partial: score, seed, R | t, passes, first score of seed 0
+
+struct TmPts {
+  const float *ax, *ay, *az, *bx, *by, *bz;       // the compacted counting positions, in LDS
+  int L, nj, lane;                                // nj = ceil(L / 64): bit j of a lane's mask stands for position lane + 64 j
+};
+
+// the at most seven fragment lengths L, L/2, L/4, ... (> 4), 4 and the number of starts 0, step, 2 step, ... <= L - len of each.
+// Slot i < 6 holds L >> i while that is above 4 (the lengths only fall, so the first one at or below 4 ends them), slot 6 the
+// closing 4; an unused slot has no starts and so takes no seed number.  Fixed slots: no dynamically indexed writes.
+struct TmSeeds {
+  int len[7], cnt[7], total;
+};
+
+__device__ __forceinline__ TmSeeds tm_seeds(int L, int seed_step) {
+  TmSeeds s;
+  s.total = 0;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const int l = i < 6 ? L >> i : 4;
+    const bool used = L >= 4 && (i == 6 || l > 4);
+    s.len[i] = l;
+    s.cnt[i] = used ? (L - l) / seed_step + 1 : 0;
+    s.total += s.cnt[i];
+  }
+  return s;
+}
+
+__device__ __forceinline__ double tm_d0(int L) { return L > 21 ? 1.24 * cbrt((double)L - 15.0) - 1.8 : 0.5; }
+
+// Optimal proper rotation of the selected positions (Horn's quaternion on the centred cross-covariance, as aligned_rmsd_kernel):
+// rt = R | t in every lane.  Every sum is the lane's run in index order, then the butterfly, whose result is the same bits in all
+// 64 lanes -- so the eigenproblem, solved redundantly by every lane, is wave-uniform without a broadcast.
+__device__ void tm_superpose(const TmPts& q, unsigned sel, double (&rt)[12]) {
+  const double n = (double)fd::wave_sum(__builtin_popcount(sel));
+  double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = 0; j < q.nj; ++j) {
+    if (!((sel >> j) & 1u)) continue;
+    const int k = q.lane + 64 * j;
+    c[0] += (double)q.ax[k];
+    c[1] += (double)q.ay[k];
+    c[2] += (double)q.az[k];
+    c[3] += (double)q.bx[k];
+    c[4] += (double)q.by[k];
+    c[5] += (double)q.bz[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) c[k] = fd::wave_sum(c[k]) / n;
+  double s[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s[k] = 0.0;
+  for (int j = 0; j < q.nj; ++j) {
+    if (!((sel >> j) & 1u)) continue;
+    const int k = q.lane + 64 * j;
+    const double ax = (double)q.ax[k] - c[0], ay = (double)q.ay[k] - c[1], az = (double)q.az[k] - c[2];
+    const double bx = (double)q.bx[k] - c[3], by = (double)q.by[k] - c[4], bz = (double)q.bz[k] - c[5];
+    s[0] += ax * bx;
+    s[1] += ax * by;
+    s[2] += ax * bz;
+    s[3] += ay * bx;
+    s[4] += ay * by;
+    s[5] += ay * bz;
+    s[6] += az * bx;
+    s[7] += az * by;
+    s[8] += az * bz;
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s[k] = fd::wave_sum(s[k]);
+  const double Sxx = s[0], Sxy = s[1], Sxz = s[2], Syx = s[3], Syy = s[4], Syz = s[5], Szx = s[6], Szy = s[7], Szz = s[8];
+  double n4[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                     {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
+                     {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
+                     {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
+  double qn[4];
+  jacobi4_largest(n4, qn);
+  const double w = qn[0], x = qn[1], y = qn[2], z = qn[3];
+  rt[0] = w * w + x * x - y * y - z * z;
+  rt[1] = 2.0 * (x * y - w * z);
+  rt[2] = 2.0 * (x * z + w * y);
+  rt[3] = 2.0 * (x * y + w * z);
+  rt[4] = w * w - x * x + y * y - z * z;
+  rt[5] = 2.0 * (y * z - w * x);
+  rt[6] = 2.0 * (x * z - w * y);
+  rt[7] = 2.0 * (y * z + w * x);
+  rt[8] = w * w - x * x - y * y + z * z;
+  rt[9] = c[3] - (rt[0] * c[0] + rt[1] * c[1] + rt[2] * c[2]);
+  rt[10] = c[4] - (rt[3] * c[0] + rt[4] * c[1] + rt[5] * c[2]);
+  rt[11] = c[5] - (rt[6] * c[0] + rt[7] * c[1] + rt[8] * c[2]);
+}
+
+// d2 of position k under rt, and the lane's selection bits for a squared cutoff
+__device__ __forceinline__ double tm_d2(const TmPts& q, const double (&rt)[12], int k) {
+  const double ax = (double)q.ax[k], ay = (double)q.ay[k], az = (double)q.az[k];
+  const double dx = (rt[0] * ax + rt[1] * ay + rt[2] * az + rt[9]) - (double)q.bx[k];
+  const double dy = (rt[3] * ax + rt[4] * ay + rt[5] * az + rt[10]) - (double)q.by[k];
+  const double dz = (rt[6] * ax + rt[7] * ay + rt[8] * az + rt[11]) - (double)q.bz[k];
+  return dx * dx + dy * dy + dz * dz;
+}
+
+__device__ __forceinline__ unsigned tm_select(const TmPts& q, const double (&rt)[12], double dc2) {
+  unsigned ns = 0;
+  for (int j = 0; j < q.nj; ++j) {
+    const int k = q.lane + 64 * j;
+    if (k >= q.L) break;
+    if (tm_d2(q, rt, k) < dc2) ns |= 1u << j;
+  }
+  return ns;
+}
+
+// score(R, t, dcut): (1/L) sum 1 / (1 + d2 / d0^2) over all counting positions; *sel (when asked for) = the positions with
+// d2 < dcut^2, dcut widened by 0.5 until at least three are selected.  The widening loop is wave-uniform and bounded
+// (TM_MAX_WIDEN); a score that is not finite (a NaN or infinite coordinate among the counting positions) can never become a
+// candidate, so its selection is not widened at all.
+__device__ double tm_score_pass(const TmPts& q, const double (&rt)[12], double d0sq, double dcut, unsigned* sel) {
+  double sum = 0.0;
+  for (int j = 0; j < q.nj; ++j) {
+    const int k = q.lane + 64 * j;
+    if (k >= q.L) break;
+    sum += 1.0 / (1.0 + tm_d2(q, rt, k) / d0sq);
+  }
+  sum = fd::wave_sum(sum) / (double)q.L;
+  if (!sel) return sum;
+  unsigned ns = tm_select(q, rt, dcut * dcut);
+  int cnt = fd::wave_sum(__builtin_popcount(ns));
+  const bool finite = sum - sum == 0.0;           // (false for NaN and for infinities; the same bits in every lane)
+  for (int widen = 0; finite && cnt < 3 && widen < TM_MAX_WIDEN; ++widen) {
+    dcut += 0.5;
+    ns = tm_select(q, rt, dcut * dcut);
+    cnt = fd::wave_sum(__builtin_popcount(ns));
+  }
+  *sel = ns;
+  return sum;
+}
+
+// Block c of pair p (blockIdx.x = p parts + c) stages the pair's counting positions once; then wave w owns the seeds
+// 4 c + w, + 4 parts, ...  No block barrier after the staging: the seeds take different numbers of refinements.
+template <int MAXN>
+__global__ __launch_bounds__(MT, 3) void tm_search_kernel(const float* __restrict__ A, long a_stride, const float* __restrict__ B,
+                                                       long b_stride, const int* __restrict__ ia, const int* __restrict__ ib,
+                                                       const float* __restrict__ mask, int N, int seed_step, int max_iter, int parts,
+                                                       double* __restrict__ ws) {
+  constexpr int PER = MAXN / MT;
+  __shared__ float pax[MAXN], pay[MAXN], paz[MAXN], pbx[MAXN], pby[MAXN], pbz[MAXN];
+  __shared__ int wave_tot[MW];
+  const int tid = (int)threadIdx.x, lane = fd::lane_id(), wave = fd::wave_id();
+  const long p = (long)(blockIdx.x / (unsigned)parts);
+  const int c = (int)(blockIdx.x % (unsigned)parts);
+  const long sa = ia ? (long)ia[p] : p, sb = ib ? (long)ib[p] : p;
+  const float* a = A + sa * N * a_stride;
+  const float* bq = B + sb * N * b_stride;
+  const float* ma = mask ? mask + sa * N : nullptr;
+  const float* mb = mask ? mask + sb * N : nullptr;
+
+  // ---- staging: thread t owns the positions [t per, (t + 1) per); backbone_metrics_kernel's prefix scan ----
+  const int per = (N + MT - 1) / MT;
+  const int r0 = tid * per;
+  unsigned present = 0;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const int r = r0 + k;
+    if (k < per && r < N && (!mask || (ma[r] != 0.f && mb[r] != 0.f))) present |= 1u << k;
+  }
+  const int cnt = __builtin_popcount(present);
+  int incl = cnt;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl(incl, lane >= o ? lane - o : lane);
+    if (lane >= o) incl += u;
+  }
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  int base = incl - cnt, L = 0;
+  for (int w = 0; w < MW; ++w) {
+    if (w < wave) base += wave_tot[w];
+    L += wave_tot[w];
+  }
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    if (present & (1u << k)) {
+      const float* pa = a + (long)(r0 + k) * a_stride;
+      const float* pb = bq + (long)(r0 + k) * b_stride;
+      pax[base] = pa[0];
+      pay[base] = pa[1];
+      paz[base] = pa[2];
+      pbx[base] = pb[0];
+      pby[base] = pb[1];
+      pbz[base] = pb[2];
+      ++base;
+    }
+  }
+  __syncthreads();
+
+  // ---- the seeds of this wave (everything below is wave-uniform; only wave collectives) ----
+  TmPts q;
+  q.ax = pax, q.ay = pay, q.az = paz, q.bx = pbx, q.by = pby, q.bz = pbz;
+  q.L = L;
+  q.nj = (L + 63) >> 6;
+  q.lane = lane;
+  const double d0 = tm_d0(L), d0sq = d0 * d0;
+  const double d0s = d0 < 4.5 ? 4.5 : (d0 > 8.0 ? 8.0 : d0);
+  double best = -1.0, best_rt[12], first0 = 0.0, rt[12];
+  int best_seed = -1;
+  long passes = 0;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) best_rt[k] = 0.0;
+
+  if (L < 4) {
+    // no search: the formula under the whole-set superposition (NaN for an empty pair), by the first wave of the first part
+    if (c == 0 && wave == 0) {
+      unsigned all = 0;
+      for (int j = 0; j < q.nj; ++j)
+        if (lane + 64 * j < L) all |= 1u << j;
+      tm_superpose(q, all, best_rt);
+      best = tm_score_pass(q, best_rt, d0sq, 0.0, nullptr);
+      first0 = best;
+    }
+  } else {
+    const TmSeeds sd = tm_seeds(L, seed_step);
+    for (int seed = 4 * c + wave; seed < sd.total; seed += 4 * parts) {
+      int rest = seed, start = 0, stop = 0;
+      bool found = false;
+#pragma unroll
+      for (int i = 0; i < 7; ++i) {
+        if (!found && rest < sd.cnt[i]) {
+          found = true;
+          start = rest * seed_step;
+          stop = start + sd.len[i];
+        } else if (!found) {
+          rest -= sd.cnt[i];
+        }
+      }
+      unsigned sel = 0;
+      for (int j = 0; j < q.nj; ++j) {
+        const int k = lane + 64 * j;
+        if (k >= start && k < stop) sel |= 1u << j;
+      }
+      tm_superpose(q, sel, rt);
+      double s = tm_score_pass(q, rt, d0sq, d0s - 1.0, &sel);
+      ++passes;
+      if (seed == 0) first0 = s;
+      bool settled = false;
+      for (int it = 0;; ++it) {
+        if (s > best) {                           // every call of score is a candidate; strictly greater: the earliest wins
+          best = s;
+          best_seed = seed;
+#pragma unroll
+          for (int k = 0; k < 12; ++k) best_rt[k] = rt[k];
+        }
+        if (settled || it >= max_iter) break;
+        unsigned next;
+        tm_superpose(q, sel, rt);
+        s = tm_score_pass(q, rt, d0sq, d0s + 1.0, &next);
+        ++passes;
+        settled = fd::wave_sum(next == sel ? 0 : 1) == 0;      // "selection unchanged": in every lane of the wave
+        sel = next;
+      }
+    }
+  }
+  if (lane == 0) {
+    double* o = ws + (((long)blockIdx.x) * MW + wave) * TM_PART;
+    o[0] = best;
+    o[1] = (double)best_seed;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[2 + k] = best_rt[k];
+    o[14] = (double)passes;
+    o[15] = first0;
+  }
+}
+
+// One wave per pair: count L again, then the partials in a fixed order -- maximum score, lowest seed on ties; integer sum of passes.
+__global__ __launch_bounds__(64) void tm_reduce_kernel(const double* __restrict__ ws, int parts, const int* __restrict__ ia,
+                                                       const int* __restrict__ ib, const float* __restrict__ mask, int N,
+                                                       int seed_step, double* __restrict__ out, double* __restrict__ transform) {
+  const int lane = fd::lane_id();
+  const long p = (long)blockIdx.x;
+  int L = N;
+  if (mask) {
+    const long sa = ia ? (long)ia[p] : p, sb = ib ? (long)ib[p] : p;
+    const float* ma = mask + sa * N;
+    const float* mb = mask + sb * N;
+    int n = 0;
+    for (int k = lane; k < N; k += 64) n += (ma[k] != 0.f && mb[k] != 0.f) ? 1 : 0;
+    L = fd::wave_sum(n);
+  }
+  const double* w = ws + p * parts * MW * TM_PART;
+  const int np = parts * MW;
+  // the lane's own partials in index order, then across the wave: the best score, then the lowest seed that has it
+  double best = -1.0, seed = -1.0, passes = 0.0;
+  int at = 0;
+  for (int k = lane; k < np; k += 64) {
+    const double s = w[(long)k * TM_PART], sd = w[(long)k * TM_PART + 1];
+    passes += w[(long)k * TM_PART + 14];
+    if (s > best || (s == best && sd < seed)) best = s, seed = sd, at = k;
+  }
+  passes = fd::wave_sum(passes);                  // (integers below 2^53: exact in any order)
+  const double top = fd::wave_max(best);
+  const double low = -fd::wave_max(best == top ? -seed : -4.0e9);
+  const TmSeeds sd = tm_seeds(L, seed_step);
+  const bool searched = L >= 4;
+  // each seed ran on exactly one wave, so one lane holds (top, low) when any candidate was finite; without a search (L < 4)
+  // the whole-set partial is the first one
+  const bool found = searched && top >= 0.0;
+  const bool mine = searched ? (found ? (best == top && seed == low) : lane == 0) : lane == 0;
+  if (mine) {
+    const double* b = w + (long)(found ? at : 0) * TM_PART;
+    const double nan = __builtin_nan("");
+    double* o = out + p * 8;
+    o[0] = (double)L;
+    o[1] = searched ? (found ? top : nan) : w[0];
+    o[2] = w[15];
+    o[3] = found ? low : -1.0;
+    o[4] = (double)sd.total;
+    o[5] = tm_d0(L);
+    o[6] = passes;
+    o[7] = 0.0;
+    if (transform) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) transform[p * 12 + k] = b[2 + k];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int fd_backbone_metrics(const float* atoms, long atom_stride, const float* res_mask, int B, int N, double* out,
@@ -411,5 +745,34 @@ extern "C" int fd_aligned_rmsd(const float* A, long a_stride, const float* B, lo
   hipLaunchKernelGGL(aligned_rmsd_kernel, dim3(P), dim3(MT), 0, (hipStream_t)stream, A, a_stride, B, b_stride, ia, ib, mask, N,
                      out, transform);
   FD_CHECK_LAUNCH("fd_aligned_rmsd");
+  return FD_OK;
+}
+
+extern "C" int fd_tm_search(const float* A, long a_stride, const float* B, long b_stride, const int* ia, const int* ib,
+                            const float* mask, int P, int N, int seed_step, int max_iter, int parts, double* ws, double* out,
+                            double* transform, void* stream) {
+  FD_CHECK_ARG(P >= 0 && N >= 0, "fd_tm_search: negative size");
+  FD_CHECK_ARG(a_stride >= 3 && b_stride >= 3, "fd_tm_search: a point stride must be at least 3 floats");
+  FD_CHECK_ARG(N <= TM_MAX_N, "fd_tm_search: N must be at most 2048");
+  FD_CHECK_ARG(seed_step >= 1, "fd_tm_search: seed_step must be at least 1");
+  FD_CHECK_ARG(max_iter >= 0, "fd_tm_search: max_iter must not be negative");
+  FD_CHECK_ARG(parts >= 1, "fd_tm_search: parts must be at least 1");
+  FD_CHECK_ARG((ia == nullptr) == (ib == nullptr), "fd_tm_search: ia and ib are given together or not at all");
+  if (P == 0 || N == 0) return FD_OK;
+  FD_CHECK_ARG((long)P * parts < (1L << 24), "fd_tm_search: P * parts must be below 2^24 (blocks of 256 threads in one grid)");
+  FD_CHECK_ARG(ws != nullptr, "fd_tm_search: null workspace (P * parts * 64 doubles)");
+  FD_CHECK_ARG(A && B && out, "fd_tm_search: null operand");
+  FD_CHECK_ARG((((uintptr_t)out) & 7u) == 0 && (((uintptr_t)transform) & 7u) == 0 && (((uintptr_t)ws) & 7u) == 0,
+               "fd_tm_search: ws, out and transform must be 8-byte aligned");
+  const dim3 grid((unsigned)((long)P * parts));
+  // One instantiation.  The kernel is bounded to three waves per SIMD (164 VGPRs, no spill; the fp64 Jacobi sweep is what fills
+  // them, and a bound of four spills), which is also what 48 KB of LDS per block admits on a 160 KB CU: a 12 KB instantiation for
+  // N <= 512 could not raise the occupancy, so there is none.
+  hipLaunchKernelGGL(tm_search_kernel<TM_MAX_N>, grid, dim3(MT), 0, (hipStream_t)stream, A, a_stride, B, b_stride, ia, ib, mask, N,
+                     seed_step, max_iter, parts, ws);
+  FD_CHECK_LAUNCH("fd_tm_search");
+  hipLaunchKernelGGL(tm_reduce_kernel, dim3(P), dim3(64), 0, (hipStream_t)stream, ws, parts, ia, ib, mask, N, seed_step, out,
+                     transform);
+  FD_CHECK_LAUNCH("fd_tm_search (reduce)");
   return FD_OK;
 }

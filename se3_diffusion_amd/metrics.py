@@ -5,9 +5,14 @@ From the reference: ca_ca_distance (analysis/metrics.py:120-125), ca_ca_clashes 
 data/utils.py::rigid_transform_3D (:519-568) -- the columns ca_ca_bond_dev, ca_ca_valid_percent, num_ca_steric_clashes and
 ca_steric_clash_percent of its metrics.csv, and the superposition of its self-consistency step.  This module's own: a peptide-bond
 (C-N) check, a CA radius of gyration (in Angstrom over the CA atoms: NOT mdtraj's radius_of_gyration column, which takes all atoms
-and reports nm), and tm_kabsch, the TM-score formula under the one least-squares superposition -- a lower bound of the TM-score
-of the given correspondence, not TM-align's value.  Not here: the DSSP fractions, mdtraj's Rg, the OpenMM
-violation losses and TM-align.
+and reports nm), tm_kabsch, the TM-score formula under the one least-squares superposition -- a lower bound of the TM-score
+of the given correspondence -- and tm_score, that TM-score itself: the maximum over superpositions, found by the seed-and-refine
+search of Zhang & Skolnick's TM-score program (fd_tm_search; the search is spelt out in include/fd_hip.h).  It is the tm_score
+column of the reference (analysis/metrics.py:44-46,104-105) for pairs whose residue-to-residue correspondence is given: sample
+against ground truth, against its refolded self, against another sample of equal length.  What is NOT here is TM-align's search
+over alignments, which the reference's tmtools.tm_align also performs; and agreement with the values tmtools or the TM-score
+program print is not verified, because neither is available to the tests -- they check a float64 restatement of the search and
+its analytic properties.  Also not here: the DSSP fractions, mdtraj's Rg and the OpenMM violation losses.
 
 Every value stays on the device as float64; only eval_rows copies to the host, once.
 """
@@ -20,6 +25,9 @@ from . import hip
 BACKBONE_SLOTS = ("num_res", "ca_ca_bond_dev", "ca_ca_valid_percent", "num_ca_steric_clashes", "ca_steric_clash_percent",
                   "ca_radius_of_gyration", "c_n_bond_dev", "c_n_bond_valid_percent", "max_ca_ca_dist")
 RMSD_SLOTS = ("num_aligned", "mean_dist", "rmsd", "tm_kabsch", "reflection", "max_dist")
+TM_SLOTS = ("num_aligned", "tm_score", "tm_kabsch", "best_seed", "num_seeds", "d0", "passes")
+TM_MAX_N = 2048          # fd_tm_search's limit (48 KB of LDS for the six coordinate arrays)
+TM_FILL_BLOCKS = 768     # blocks resident at once on the 256 CUs of an MI355X: three per CU (164 VGPRs, 48 KB of LDS each)
 CA = 1                   # slot of CA in atom37 / the compact [.,5,3] order N, CA, C, CB, O
 
 
@@ -106,8 +114,9 @@ def aligned_rmsd(pos_1, pos_2, mask=None, return_transform=False):
 
 def pairwise_rmsd(pos, mask=None):
     """All-pairs superposed distances of M point sets pos [M,N,3] (mask [M,N]: a position counts in a pair iff it is non-zero in
-    both sets): dict of float64 [M,M] device tensors mean_dist, rmsd, tm_kabsch -- the quantity sample diversity is computed
-    from.  One launch over the M (M - 1) / 2 upper pairs; the result is mirrored, the diagonal is 0, 0 and 1."""
+    both sets): dict of float64 [M,M] device tensors mean_dist, rmsd, tm_kabsch.  tm_kabsch is only a lower bound of a pair's
+    TM-score; the matrix that diversity clustering at a TM-score threshold starts from is pairwise_tm's.  One launch over the
+    M (M - 1) / 2 upper pairs; the result is mirrored, the diagonal is 0, 0 and 1."""
     if pos.dim() != 3:
         raise ValueError(f"points of shape {tuple(pos.shape)}: expected [M,N,3]")
     M = pos.shape[0]
@@ -127,12 +136,99 @@ def pairwise_rmsd(pos, mask=None):
     return res
 
 
-def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None):
+def tm_num_seeds(L, seed_step=1):
+    """Number of seeds fd_tm_search tries on L counting positions (include/fd_hip.h): the fragment lengths L, L >> 1, ... while above
+    4 (at most six), then 4; for each the starts 0, seed_step, ... <= L - length.  0 below four positions."""
+    if L < 4:
+        return 0
+    lens, l = [], L
+    for i in range(6):
+        if l <= 4:
+            break
+        lens.append(l)
+        l = L >> (i + 1)
+    lens.append(4)
+    return sum((L - l) // seed_step + 1 for l in lens)
+
+
+def tm_parts(P, N, seed_step=1):
+    """How many blocks share the seeds of one pair when the caller does not say: enough for P * parts to reach TM_FILL_BLOCKS
+    when there are few pairs, never more than ceil(seeds / 4) (a block's four waves would have nothing to do).  From N, not from
+    the masks, so nothing is read back; the result does not depend on it bit for bit."""
+    if P <= 0:
+        return 1
+    return max(1, min(-(-tm_num_seeds(N, seed_step) // 4), -(-TM_FILL_BLOCKS // P)))
+
+
+def _tm_call(pos_1, pos_2, mask, ia, ib, P, seed_step, max_iter, parts, want_transform):
+    a, a_stride = _points(pos_1)
+    b, b_stride = _points(pos_2)
+    N = a.shape[1]
+    dev = a.device
+    if mask is not None:
+        mask = _f32c(mask.reshape(-1, N))
+    if parts is None:
+        parts = tm_parts(P, N, max(1, int(seed_step)))
+    out = torch.empty((P, 8), dtype=torch.float64, device=dev)
+    tr = torch.empty((P, 12), dtype=torch.float64, device=dev) if want_transform else None
+    ws = torch.empty((P * max(1, int(parts)) * 64,), dtype=torch.float64, device=dev)      # FD_TM_WS_DOUBLES
+    hip.get_lib().call("fd_tm_search", a, a_stride, b, b_stride, ia, ib, mask, P, N, seed_step, max_iter, parts, ws, out, tr)
+    return out, tr
+
+
+def tm_score(pos_1, pos_2, mask=None, seed_step=1, max_iter=20, return_transform=False, parts=None):
+    """TM-score of pos_1 against pos_2 ([P,N,3] or [N,3]; a strided view such as atom37[:, :, 1] is read in place) under the GIVEN
+    correspondence, position k to position k: the maximum over superpositions of the TM-score formula, found by the seed-and-refine
+    search of the TM-score program (include/fd_hip.h spells it out), normalised by the number of counting positions.  Not
+    TM-align: no search over alignments.  mask [P,N] (or [N]): the positions that count.  seed_step: distance between the starts of
+    the seed fragments (1 = every start; a coarser step searches a subset of the seeds, so it can only lower the score); max_iter:
+    refinements per seed; parts: blocks per pair (None: tm_parts; the result does not depend on it bit for bit).  dict name ->
+    float64 device tensor [P] (0-d without P) under TM_SLOTS; return_transform adds R [P,3,3] and t [P,3] of the best superposition,
+    aligned = R a + t.  N <= 2048.  Two launches (search, reduce), no host synchronisation."""
+    batched = pos_1.dim() == 3
+    if not batched:
+        pos_1, pos_2 = pos_1[None], pos_2[None]
+        mask = None if mask is None else mask[None]
+    if pos_1.shape != pos_2.shape:
+        raise ValueError(f"point sets of shapes {tuple(pos_1.shape)} and {tuple(pos_2.shape)}")
+    P = pos_1.shape[0]
+    out, tr = _tm_call(pos_1, pos_2, mask, None, None, P, seed_step, max_iter, parts, return_transform)
+    pick = (lambda x: x) if batched else (lambda x: x[0])
+    res = {name: pick(out[:, k]) for k, name in enumerate(TM_SLOTS)}
+    if return_transform:
+        res["R"] = pick(tr[:, :9].reshape(P, 3, 3))
+        res["t"] = pick(tr[:, 9:])
+    return res
+
+
+def pairwise_tm(pos, mask=None, seed_step=1, max_iter=20):
+    """All-pairs TM-scores (tm_score) of M point sets pos [M,N,3] (mask [M,N]: a position counts in a pair iff it is non-zero in both
+    sets): float64 [M,M] device tensor, the matrix diversity clustering starts from.  One search over the M (M - 1) / 2 upper
+    pairs; the result is mirrored (with equal lengths and a fixed correspondence the normalisation is the same both ways; the
+    search itself runs set i onto set j, i < j), the diagonal is 1."""
+    if pos.dim() != 3:
+        raise ValueError(f"points of shape {tuple(pos.shape)}: expected [M,N,3]")
+    M = pos.shape[0]
+    dev = pos.device
+    iu = torch.triu_indices(M, M, 1, device=dev)
+    ia, ib = iu[0].to(torch.int32).contiguous(), iu[1].to(torch.int32).contiguous()
+    out, _ = _tm_call(pos, pos, mask, ia, ib, ia.numel(), seed_step, max_iter, None, False)
+    m = torch.zeros((M, M), dtype=torch.float64, device=dev)
+    v = out[:, TM_SLOTS.index("tm_score")]
+    m[iu[0], iu[1]] = v
+    m[iu[1], iu[0]] = v
+    m.fill_diagonal_(1.0)
+    return m
+
+
+def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False):
     """One dict of Python floats per backbone with the reference's column names (Experiment.eval_fn,
     experiments/train_se3_diffusion.py:475-508, and CA_VIOLATION_METRICS): ca_ca_bond_dev, ca_ca_valid_percent,
     ca_steric_clash_percent, num_ca_steric_clashes, num_res, fixed_residues, diffused_percentage -- and this module's own
     BACKBONE_SLOTS.  gt_atom37 adds aligned_rmsd_to_gt (calc_aligned_rmsd of the sample's CA onto the ground truth's) over the
-    diffused present residues (analysis/metrics.py:100-102).  One device-to-host copy."""
+    diffused present residues (analysis/metrics.py:100-102); with tm=True it also adds tm_score_to_gt, tm_score over the same
+    residues, normalised by their number -- the ground truth's length under the reference's own masking (metrics.py:100-105).
+    One device-to-host copy."""
     B, N = atom37.shape[:2]
     res_mask = res_mask.reshape(B, N).to(torch.float32)
     fixed = torch.zeros_like(res_mask) if fixed_mask is None else fixed_mask.reshape(B, N).to(torch.float32)
@@ -143,6 +239,8 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None):
         diffused = (1.0 - fixed) * (res_mask != 0)
         out, _ = _rmsd_call(a37[:, :, CA], g37[:, :, CA], diffused, None, None, B, False)
         cols.append(out)
+        if tm:
+            cols.append(_tm_call(a37[:, :, CA], g37[:, :, CA], diffused, None, None, B, 1, 20, None, False)[0])
     host = torch.cat(cols, dim=1).cpu()
     rows = []
     for b in range(B):
@@ -153,5 +251,7 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None):
         row["diffused_percentage"] = (n - v[12]) / n if n else float("nan")
         if gt_atom37 is not None:
             row["aligned_rmsd_to_gt"] = v[13 + RMSD_SLOTS.index("mean_dist")]
+            if tm:
+                row["tm_score_to_gt"] = v[21 + TM_SLOTS.index("tm_score")]
         rows.append(row)
     return rows

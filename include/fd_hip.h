@@ -778,6 +778,76 @@ int fd_aligned_rmsd(const float* A, long a_stride, const float* B, long b_stride
 int fd_tm_search(const float* A, long a_stride, const float* B, long b_stride, const int* ia, const int* ib, const float* mask,
                  int P, int N, int seed_step, int max_iter, int parts, double* ws, double* out, double* transform, void* stream);
 
+/* ---- secondary structure and the shape columns (se3_diffusion_amd/csrc/fd_dssp.hip) ----
+ * Kabsch & Sander (1983) in the order the DSSP program applies it, and the reference's SHAPE_METRICS (analysis/metrics.py:37-42:
+ * coil_percent, helix_percent, strand_percent, radius_of_gyration; non_coil_percent from calc_mdtraj_metrics, :58-69), which the
+ * reference takes from md.compute_dssp(simplified=True) and md.compute_rg on a PDB file it writes per sample.  Two launches, one
+ * per entry point; operands as fd_backbone_metrics (residue r of backbone b at atoms + (b N + r) atom_stride floats, N, CA, C, CB,
+ * O in slots 0..4, read in place; present iff res_mask[b,r] != 0; B == 0 or N == 0 returns FD_OK without a launch and writes
+ * nothing).  N <= FD_DSSP_MAX_N = 2048: the H-bond kernel keeps C, O and CA of a whole chain in LDS (nine fp32 arrays, 72 KB, and
+ * 8 KB of index maps: 80 KB of the 160 KB of a CU); 4096 would need 160 KB and does not fit.  The assignment kernel needs 43 KB.
+ * NOT verified: no DSSP program and no mdtraj is available to this project, so agreement with the letters md.compute_dssp prints
+ * has never been checked; the tests check a float64 restatement of the text below and its plausibility against the HELIX / SHEET
+ * records of six deposited structures.  Two deliberate differences from the DSSP program: the energy is NOT rounded to three
+ * decimals, and the two gaps of a bulge must be non-negative (the program's own comparison is remembered as accepting negative
+ * gaps; that form glued the strands of a meander into one stretch).
+ *
+ * All decisions are made in fp64 from the fp32 coordinates.
+ *   residues      the present residues, compacted in index order; every index below is a compacted index, 0 .. n-1.
+ *   chain break   between a and a+1 iff their original indices are not adjacent or |C(a) - N(a+1)| > 2.5 A.  nobreak(a, b): both
+ *                 in 0 .. n-1, a <= b, and no break anywhere in a .. b.
+ *   amide H       H(i) = N(i) + (C(i-1) - O(i-1)) / |C(i-1) - O(i-1)|.  i is a donor only if i > 0, there is no break before i and
+ *                 no_donor[b,i] (optional, [B,N], by original index: prolines) is zero.
+ *   energy        of donor i and acceptor j != i, j != i-1, with |CA(i) - CA(j)| < 9 A:
+ *                 E = 27.888 (1/d(N,O) + 1/d(H,C) - 1/d(H,O) - 1/d(N,C)) kcal/mol, N and H of i, C and O of j;
+ *                 E = -9.9 if any of the four distances is below 0.5 A, and E is clamped below at -9.9.  No rounding.
+ *   acceptors     every donor keeps its two lowest energies and their acceptors; equal energies go to the lower index.
+ *                 hb(a, b): b is one of a's two kept acceptors and its E < -0.5.  Nothing else of the energies is used below.
+ *   turns         turn_n(i), n = 3, 4, 5: hb(i+n, i) and nobreak(i, i+n).
+ *   bridges       for i >= 1, j >= i+3, j <= n-2, nobreak(i-1, i+1) and nobreak(j-1, j+1): parallel if (hb(i+1, j) and hb(j, i-1))
+ *                 or (hb(j+1, i) and hb(i, j-1)); otherwise antiparallel if (hb(i+1, j-1) and hb(j+1, i-1)) or (hb(j, i) and
+ *                 hb(i, j)).
+ *   ladders       maximal runs of bridges of one type: (i, j), (i+1, j+1), ... parallel; (i, j), (i+1, j-1), ... antiparallel.
+ *                 (The conditions of a bridge keep a run from crossing a break.)
+ *   bulges        two ladders of one type, the first the one whose i-strand starts lower; a strand's start and end are its lowest
+ *                 and highest residue.  gi = residues between them on the i-strand = second's i-start - first's i-end - 1; gj =
+ *                 residues between them on the j-strand = second's j-start - first's j-end - 1 (parallel), first's j-start -
+ *                 second's j-end - 1 (antiparallel: the second ladder's j-strand lies below the first's).  Linked iff gi >= 0,
+ *                 gj >= 0, no break in either gap, and (gi <= 1 and gj <= 4) or (gi <= 4 and gj <= 1).  Linking is transitive.
+ *   sheets        on each of the two strands of a group of linked ladders every residue from the strand's lowest to its highest
+ *                 gets E if the group holds more than one bridge, else B.  E overrides B.
+ *   helices       after the sheets: H on i .. i+3 wherever turn_4(i-1) and turn_4(i), over anything; then G on i .. i+2 wherever
+ *                 turn_3(i-1) and turn_3(i) and all three are blank or G; then I on i .. i+4 wherever turn_5(i-1) and turn_5(i)
+ *                 and all five are blank or I.
+ *   T             blank residues i with turn_n(k) for some n and some i-n < k < i.
+ *   S             remaining blank residues i with nobreak(i-2, i+2) whose angle between CA(i) - CA(i-2) and CA(i+2) - CA(i) is
+ *                 above 70 degrees.
+ *   classes       H, G, I -> helix; E, B -> strand; everything else coil (mdtraj's simplified=True).
+ *
+ * fd_dssp_hbonds(..): acc_idx [B,N,2] int32, the ORIGINAL residue indices of the two kept acceptors of the donor at original
+ * index r, lowest energy first (-1: none -- not present, not a donor, or fewer candidates); acc_e [B,N,2] fp64 their energies
+ * (0 where acc_idx is -1).  Every element is written. */
+#define FD_DSSP_MAX_N 2048
+int fd_dssp_hbonds(const float* atoms, long atom_stride, const float* res_mask, const float* no_donor, int B, int N, int* acc_idx,
+                   double* acc_e, void* stream);
+
+/* The assignment from fd_dssp_hbonds' table, one block per backbone.  natoms: atoms per residue (37 or 5; 3 natoms <= atom_stride),
+ * for the radius of gyration.  ss [B,N] int8, by original index:
+ *   -1 absent, 0 blank, 1 H, 2 B, 3 E, 4 G, 5 I, 6 T, 7 S
+ * out[b][0..8) =
+ *   0 num_res             n
+ *   1 helix_percent       residues of class helix / n
+ *   2 strand_percent      residues of class strand / n
+ *   3 coil_percent        the rest / n
+ *   4 non_coil_percent    slot 1 + slot 2
+ *   5 radius_of_gyration  sqrt(mean |x - mean x|^2) over all atoms of the present residues whose three coordinates are not all
+ *                         zero, in nm (Angstrom / 10): mdtraj's unit-mass compute_rg on the PDB the reference would have written
+ *   6 num_hbonds          kept acceptors with E < -0.5
+ *   7 overflow            1.0 iff the chain has more than 2048 ladders and some were dropped (never silently), else 0
+ * n == 0 gives NaN in slots 1..5.  Chains too short for any structure (n < 6) give blank, T and S letters, not an error. */
+int fd_dssp_assign(const float* atoms, long atom_stride, int natoms, const float* res_mask, const int* acc_idx, const double* acc_e,
+                   int B, int N, signed char* ss, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -287,6 +287,8 @@ _SIGS = {
     "fd_backbone_metrics": "plpiips",
     "fd_aligned_rmsd": "plplpppiipps",
     "fd_tm_search": "plplppp" + "iiiii" + "ppp" + "s",
+    "fd_dssp_hbonds": "plppiipps",
+    "fd_dssp_assign": "plipppiipps",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

@@ -12,7 +12,16 @@ column of the reference (analysis/metrics.py:44-46,104-105) for pairs whose resi
 against ground truth, against its refolded self, against another sample of equal length.  What is NOT here is TM-align's search
 over alignments, which the reference's tmtools.tm_align also performs; and agreement with the values tmtools or the TM-score
 program print is not verified, because neither is available to the tests -- they check a float64 restatement of the search and
-its analytic properties.  Also not here: the DSSP fractions, mdtraj's Rg and the OpenMM violation losses.
+its analytic properties.
+
+secondary_structure: the reference's SHAPE_METRICS (analysis/metrics.py:37-42, :58-69) -- coil_percent, helix_percent,
+strand_percent, non_coil_percent from Kabsch & Sander's assignment (fd_dssp_hbonds, fd_dssp_assign; include/fd_hip.h is the
+specification) and radius_of_gyration as mdtraj's compute_rg defines it (all atoms, unit mass, nm) -- without the PDB file, mdtraj
+and the host round trip of the reference.  NOT verified: no DSSP program and no mdtraj exists where this project is built, so
+agreement with the letters md.compute_dssp prints has never been checked; the tests check a float64 restatement and its
+plausibility against the HELIX / SHEET records of six deposited structures.  Two deliberate differences from the DSSP program:
+the H-bond energy is not rounded to three decimals, and the gaps of a bulge must be non-negative.  Still not here (DESIGN.md
+section 8): the OpenMM violation losses, solvent accessibility, and the sheet-label and bridge-partner columns of a DSSP record.
 
 Every value stays on the device as float64; only eval_rows copies to the host, once.
 """
@@ -28,6 +37,11 @@ RMSD_SLOTS = ("num_aligned", "mean_dist", "rmsd", "tm_kabsch", "reflection", "ma
 TM_SLOTS = ("num_aligned", "tm_score", "tm_kabsch", "best_seed", "num_seeds", "d0", "passes")
 TM_MAX_N = 2048          # fd_tm_search's limit (48 KB of LDS for the six coordinate arrays)
 TM_FILL_BLOCKS = 768     # blocks resident at once on the 256 CUs of an MI355X: three per CU (164 VGPRs, 48 KB of LDS each)
+SHAPE_SLOTS = ("num_res", "helix_percent", "strand_percent", "coil_percent", "non_coil_percent", "radius_of_gyration",
+               "num_hbonds", "overflow")
+SHAPE_COLUMNS = ("coil_percent", "helix_percent", "strand_percent", "non_coil_percent", "radius_of_gyration")    # the reference's names
+DSSP_MAX_N = 2048        # FD_DSSP_MAX_N: fd_dssp_hbonds keeps C, O and CA of a whole chain in LDS (80 KB of a CU's 160 KB)
+SS_LETTERS = " HBEGITS"  # fd_dssp_assign's codes 0..7 (-1: the residue is absent)
 CA = 1                   # slot of CA in atom37 / the compact [.,5,3] order N, CA, C, CB, O
 
 
@@ -64,6 +78,70 @@ def backbone_metrics(atoms, res_mask=None, out=None):
         res_mask = None if res_mask is None else res_mask[None]
     blk = _backbone_block(atoms, res_mask, out)
     return {name: (blk[:, k] if batched else blk[0, k]) for k, name in enumerate(BACKBONE_SLOTS)}
+
+
+def _dssp_call(atoms, res_mask, no_donor):
+    """fd_dssp_hbonds then fd_dssp_assign on atoms [B,N,A,3]: ss int8 [B,N], out float64 [B,8], acc_idx int32 [B,N,2], acc_e float64 [B,N,2]"""
+    if atoms.dim() != 4 or atoms.shape[-1] != 3 or atoms.shape[-2] not in (5, 37):
+        raise ValueError(f"atoms of shape {tuple(atoms.shape)}: expected [B,N,37,3] or [B,N,5,3] (or the same without B)")
+    B, N, A = atoms.shape[:3]
+    if N > DSSP_MAX_N:
+        raise ValueError(f"secondary_structure: N = {N} residues, at most {DSSP_MAX_N} are supported")
+    atoms = _f32c(atoms)
+    dev = atoms.device
+    if res_mask is None:
+        res_mask = (atoms != 0).reshape(B, N, A * 3).any(-1)
+    res_mask = _f32c(res_mask.reshape(B, N))
+    if no_donor is not None:
+        no_donor = _f32c(no_donor.reshape(B, N))
+    acc_idx = torch.empty((B, N, 2), dtype=torch.int32, device=dev)
+    acc_e = torch.empty((B, N, 2), dtype=torch.float64, device=dev)
+    ss = torch.empty((B, N), dtype=torch.int8, device=dev)
+    if N == 0:
+        # the entry points launch nothing on an empty chain: num_res 0, the means over no residues NaN, no bonds, no overflow
+        out = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev)
+        out[:, 0] = 0.0
+        out[:, 6:] = 0.0
+        return ss, out, acc_idx, acc_e
+    out = torch.empty((B, 8), dtype=torch.float64, device=dev)
+    lib = hip.get_lib()
+    lib.call("fd_dssp_hbonds", atoms, A * 3, res_mask, no_donor, B, N, acc_idx, acc_e)
+    lib.call("fd_dssp_assign", atoms, A * 3, A, res_mask, acc_idx, acc_e, B, N, ss, out)
+    return ss, out, acc_idx, acc_e
+
+
+def secondary_structure(atoms, res_mask=None, no_donor=None, return_hbonds=False):
+    """Kabsch & Sander's secondary structure of atoms [B,N,37,3] or [B,N,5,3] (atom order N, CA, C, CB, O; or the same without B)
+    and the reference's shape columns: dict with ss (int8 [B,N]: -1 absent, 0 blank, 1 H, 2 B, 3 E, 4 G, 5 I, 6 T, 7 S), ss3
+    (int8: -1 absent, 0 C, 1 H, 2 E -- mdtraj's simplified classes) and a float64 device tensor [B] (0-d without B) per name of
+    SHAPE_SLOTS (radius_of_gyration over all atoms, in nm).  res_mask as backbone_metrics; no_donor [B,N]: non-zero where the
+    residue has no amide hydrogen (prolines).  return_hbonds adds acc_idx (int32 [B,N,2], each donor's two best acceptors by
+    residue index, -1 if none) and acc_e (float64, kcal/mol).  include/fd_hip.h is the specification and says what is not
+    verified.  N <= 2048, or ValueError before anything is launched.  Two launches, no host synchronisation."""
+    batched = atoms.dim() == 4
+    if not batched:
+        atoms = atoms[None]
+        res_mask = None if res_mask is None else res_mask[None]
+        no_donor = None if no_donor is None else no_donor[None]
+    ss, out, acc_idx, acc_e = _dssp_call(atoms, res_mask, no_donor)
+    helix, strand = (ss == 1) | (ss == 4) | (ss == 5), (ss == 2) | (ss == 3)
+    ss3 = (helix.to(torch.int8) + 2 * strand.to(torch.int8)).masked_fill_(ss < 0, -1)      # (fills on the device: nothing is uploaded)
+    pick = (lambda x: x) if batched else (lambda x: x[0])
+    res = {"ss": pick(ss), "ss3": pick(ss3)}
+    res.update({name: pick(out[:, k]) for k, name in enumerate(SHAPE_SLOTS)})
+    if return_hbonds:
+        res["acc_idx"] = pick(acc_idx)
+        res["acc_e"] = pick(acc_e)
+    return res
+
+
+def ss_string(codes, classes=False):
+    """Host helper (copies to the host): the usual one-letter strings of secondary_structure's ss codes, [N] -> str, [B,N] -> list
+    of str: H B E G I T S, a blank for a blank residue, '-' for an absent one.  classes=True reads the codes as ss3: C H E."""
+    rows = torch.as_tensor(codes).cpu().tolist()
+    letters = "CHE" if classes else SS_LETTERS
+    one = lambda row: "".join("-" if c < 0 else letters[c] for c in row)
+    return one(rows) if rows == [] or not isinstance(rows[0], list) else [one(r) for r in rows]
 
 
 def _points(pos):
@@ -221,14 +299,15 @@ def pairwise_tm(pos, mask=None, seed_step=1, max_iter=20):
     return m
 
 
-def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False):
+def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape=False):
     """One dict of Python floats per backbone with the reference's column names (Experiment.eval_fn,
     experiments/train_se3_diffusion.py:475-508, and CA_VIOLATION_METRICS): ca_ca_bond_dev, ca_ca_valid_percent,
     ca_steric_clash_percent, num_ca_steric_clashes, num_res, fixed_residues, diffused_percentage -- and this module's own
     BACKBONE_SLOTS.  gt_atom37 adds aligned_rmsd_to_gt (calc_aligned_rmsd of the sample's CA onto the ground truth's) over the
     diffused present residues (analysis/metrics.py:100-102); with tm=True it also adds tm_score_to_gt, tm_score over the same
     residues, normalised by their number -- the ground truth's length under the reference's own masking (metrics.py:100-105).
-    One device-to-host copy."""
+    shape=True adds the reference's SHAPE_METRICS and non_coil_percent (SHAPE_COLUMNS; secondary_structure without a proline
+    mask, as the backbone carries no sequence).  One device-to-host copy."""
     B, N = atom37.shape[:2]
     res_mask = res_mask.reshape(B, N).to(torch.float32)
     fixed = torch.zeros_like(res_mask) if fixed_mask is None else fixed_mask.reshape(B, N).to(torch.float32)
@@ -241,6 +320,9 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False):
         cols.append(out)
         if tm:
             cols.append(_tm_call(a37[:, :, CA], g37[:, :, CA], diffused, None, None, B, 1, 20, None, False)[0])
+    if shape:
+        shape_at = sum(c.shape[1] for c in cols)
+        cols.append(_dssp_call(atom37, res_mask, None)[1])
     host = torch.cat(cols, dim=1).cpu()
     rows = []
     for b in range(B):
@@ -253,5 +335,7 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False):
             row["aligned_rmsd_to_gt"] = v[13 + RMSD_SLOTS.index("mean_dist")]
             if tm:
                 row["tm_score_to_gt"] = v[21 + TM_SLOTS.index("tm_score")]
+        if shape:
+            row.update({name: v[shape_at + SHAPE_SLOTS.index(name)] for name in SHAPE_COLUMNS})
         rows.append(row)
     return rows

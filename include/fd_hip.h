@@ -739,9 +739,9 @@ int fd_aligned_rmsd(const float* A, long a_stride, const float* B, long b_stride
 /* The TM-score of P pairs under their GIVEN residue-to-residue correspondence, by the superposition search of Zhang & Skolnick's
  * TM-score program: the tm_score column of the reference's EVAL_METRICS (analysis/metrics.py:44-46,104-105) for pairs whose
  * correspondence is fixed -- sample against ground truth, against its refolded self, against another sample of equal length.
- * NOT TM-align: the reference calls tmtools.tm_align, which also searches over alignments; that search is not here, and agreement
- * with the printed values of tmtools or of the TM-score program has not been verified (neither is available to this project's
- * tests; they check a float64 restatement of the search below).  Operands as fd_aligned_rmsd (strided points read in place,
+ * NOT TM-align: the reference calls tmtools.tm_align, which also searches over alignments; that search is fd_tm_align below, which
+ * runs this search on the pair lists it builds.  Agreement with the printed values of tmtools or of the TM-score program has not
+ * been verified for either (neither is available to this project's tests; they check a float64 restatement of the search below).  Operands as fd_aligned_rmsd (strided points read in place,
  * ia / ib together or not at all, mask rows indexed like the sets, 8-byte aligned fp64 operands, P == 0 or N == 0 returns FD_OK
  * without a launch); N <= 2048, seed_step >= 1, max_iter >= 0, parts >= 1 and a non-null ws, or the call is refused.
  *
@@ -777,6 +777,94 @@ int fd_aligned_rmsd(const float* A, long a_stride, const float* B, long b_stride
 #define FD_TM_WS_DOUBLES(P, parts) ((long)(P) * (long)(parts) * 64L)
 int fd_tm_search(const float* A, long a_stride, const float* B, long b_stride, const int* ia, const int* ib, const float* mask,
                  int P, int N, int seed_step, int max_iter, int parts, double* ws, double* out, double* transform, void* stream);
+
+/* ---- TM-align: the search over alignments (se3_diffusion_amd/csrc/fd_tm_align.hip) ----
+ * The alignment search of TM-align (Zhang & Skolnick 2005) as restated below, for chains of any two lengths: what the reference's
+ * tm_score column (analysis/metrics.py:44-46,104-105, tmtools.tm_align) computes.  Agreement with the values tmtools prints is NOT
+ * verified: tmtools does not exist where this project is built and tested.  Verified are a float64 restatement of this text,
+ * analytic properties (rigid copies, deletions, identical chains) and plausibility on deposited chains.  Deliberate
+ * simplifications are listed at the end.  All decisions are made in fp64 from the fp32 coordinates; distance cut-offs use strict <
+ * on squared distances, as fd_tm_search does.
+ *
+ * Operands.  Point sets A [*,Na,3] and B [*,Nb,3] with point strides, read in place as in fd_tm_search.  mask_a [*,Na], mask_b
+ * [*,Nb] (optional, indexed like the sets): the counting positions of a set are those with a non-zero mask, compacted in index
+ * order; their numbers are La and Lb.  Padded positions are never read for arithmetic (NaN there does not leak).  Pair p aligns set
+ * ia[p] of A to set ib[p] of B (both NULL: set p of both).  Na, Nb <= FD_TM_ALIGN_MAX_N.  Every index below is a compacted index;
+ * Lmin = min(La, Lb).
+ *
+ * Constants.  d0(L) = 1.24 cbrt(L - 15) - 1.8 for L > 21, else 0.5.  Search phase: d0 = d0(Lmin) + 0.8, d0s = min(max(d0, 4.5), 8),
+ * d8 = 1.5 Lmin^0.3 + 3.5.
+ *
+ *   search(pairs, Lnorm, d0, step)   fd_tm_search's per-seed procedure on the list of aligned pairs (n of them): the same fragment
+ *                  lengths (n, n >> 1, ... while above 4, then 4), seeds (starts 0, step, 2 step, ... <= n - length), score with its
+ *                  widening, and cut-offs d0s - 1 and d0s + 1 with d0s = min(max(d0, 4.5), 8) of the d0 GIVEN, max_iter 20; the sum is
+ *                  divided by Lnorm, not by n.  n < 4: one superposition of all pairs, no seeds.  Returns the best (s, R, t); ties as
+ *                  in fd_tm_search (earliest within a seed, lowest seed).
+ *   quick(alignment)   n pairs; n < 3 gives -1.  Superpose all pairs: s1 = (1/Lmin) sum 1 / (1 + d2 / d0^2).  Select d2 < d0s^2; if
+ *                  at least 3 pairs are selected, superpose the selection and score all pairs: s2.  From THOSE distances select
+ *                  d2 < (d0s + 1)^2; if at least 3, the same again: s3.  A selection below 3 stops the chain.  The result is the
+ *                  greatest of these, the earliest on ties, with its (R, t).
+ *   DP(S, gap)     val[0][*] = val[*][0] = 0 and path false there.  For i = 1..La, j = 1..Lb: h = val[i-1][j-1] + S(i-1, j-1);
+ *                  v = val[i-1][j] + (path[i-1][j] ? gap : 0); z = val[i][j-1] + (path[i][j-1] ? gap : 0); if h >= max(v, z) then
+ *                  path = true, val = h, else path = false, val = max(v, z).  Traceback from (La, Lb) while i > 0 and j > 0: if
+ *                  path[i][j], align (i-1, j-1) and step diagonally; otherwise h = val[i-1][j] + (path[i-1][j] ? gap : 0),
+ *                  v = val[i][j-1] + (path[i][j-1] ? gap : 0), and j-- if v >= h, else i--.  A gap costs only where it opens after a
+ *                  match; end gaps are free.
+ *   CA secondary structure   for i = 2 .. L-3, with d13 = |x[i-2] - x[i]|, d14 = |x[i-2] - x[i+1]|, d15 = |x[i-2] - x[i+2]|,
+ *                  d24 = |x[i-1] - x[i+1]|, d25 = |x[i-1] - x[i+2]|, d35 = |x[i] - x[i+2]|: H if |d15 - 6.37|, |d14 - 5.18|,
+ *                  |d25 - 5.18|, |d13 - 5.45|, |d24 - 5.45|, |d35 - 5.45| are all < 2.1; else E if |d15 - 13|, |d14 - 10.4|,
+ *                  |d25 - 10.4|, |d13 - 6.1|, |d24 - 6.1|, |d35 - 6.1| are all < 1.42; else T if d15 < 8; else C.  The two residues
+ *                  at each end are C.  E(i, j) = 1 if the classes of a_i and b_j are equal, else 0.
+ *
+ * Four initial alignments (candidate classes):
+ *   0 gapless      the offsets k, ascending, with a_i <-> b_{i+k} and an overlap >= m = min(Lmin, max(Lmin / 2, 5)) (integer
+ *                  division); the one of the greatest quick wins, the lowest k on ties; its (R0, t0) is kept.
+ *   1 secondary structure                   DP(E, -1).
+ *   2 secondary structure + superposition   DP(1 / (1 + d2 / d0^2) under (R0, t0) + 0.5 E, -1).
+ *   3 fragments    f = min(20, Lmin / 3); the class is empty if f < 4.  Starts in a: 0, ja, 2 ja, ... <= La - f with
+ *                  ja = max(f, ceil((La - f + 1) / 8)); in b likewise.  For each (sa, sb) in row-major order: superpose the two
+ *                  fragments, DP(1 / (1 + d2 / (d0 + 1.5)^2), 0); the alignment of the greatest quick wins, the lowest unit on ties.
+ * Refinement of each candidate map0 (skipped below 3 pairs): best = (s, R, t, map0) from search(map0, Lmin, d0, search_step).  For
+ * gap in (-0.6, 0): (R, t) = best's, prev = map0, s_old = none; up to max_dp times: new = DP(1 / (1 + d2 / d0^2) under (R, t), gap);
+ * stop if new == prev; prev = new; stop if new has fewer than 3 pairs; (s, R, t) = search(new, Lmin, d0, search_step); if
+ * s > best.s, best = (s, R, t, new); stop if s_old exists and |s - s_old| < 1e-6; s_old = s.
+ * Final: the candidate of the greatest best.s (the lowest class on ties); under its (R, t) the pairs with d > d8 are dropped
+ * (d2 <= d8^2 stays); then search(pairs, La, d0(La), 1) and search(pairs, Lb, d0(Lb), 1) on the rest.
+ *
+ * out[p][0..16) =
+ *   0 La   1 Lb
+ *   2 num_aligned   pairs after the d8 filter
+ *   3 tm_norm_a     4 tm_norm_b (the reference's column when b is the ground truth)
+ *   5 rmsd          of the kept pairs under slot 4's superposition
+ *   6 d0_a = d0(La)   7 d0_b = d0(Lb)
+ *   8 best_class
+ *   9 num_dp        DPs run in refinement over all classes (an exact integer; the cost unit of a pair)
+ *   10 num_units    gapless offsets + fragment pairs
+ *   11 search_tm    best.s
+ *   12..15          0
+ * map [P,Na] int32: for each ORIGINAL position of a the original position in b, or -1; every element is written.  transform
+ * (optional) [P][12]: slot 4's superposition, R row-major then t.  Lmin == 0 and 1 <= Lmin <= 4: no alignment is attempted -- NaN in
+ * slots 3, 4, 5, 11, best_class -1, num_dp and num_units 0, map all -1.  A candidate whose score is not finite (a non-finite
+ * coordinate among the counting positions) can never win, as in fd_tm_search; if no class has a candidate the pair is written like
+ * a short one.
+ *
+ * Three launches (seed: grid P * parts, the gapless offsets and fragment pairs dealt to waves round-robin; refine: P * 4, one block
+ * per class; final: P), no host synchronisation, no floating-point atomics, every reduction in a fixed order: results are bitwise
+ * reproducible and bitwise independent of parts and of what else is in the batch.  ws: FD_TM_ALIGN_WS_BYTES(P, parts, Na, Nb) bytes,
+ * 8-byte aligned, need not be initialised.  Refused before any launch: Na or Nb above the limit, search_step < 1, max_dp < 0,
+ * parts < 1, ia without ib (or the reverse), and -- unless P == 0, Na == 0 or Nb == 0, which return FD_OK without a launch -- a
+ * null ws, out or map.
+ *
+ * Simplifications against the TM-align program: no smoothing of the secondary-structure string; no d8 cut inside the search-phase
+ * score; no fragment-threading class (get_initial_fgt); the fragment class runs on at most 8 x 8 starts; no sequence identity, no
+ * circular permutation, no fast mode. */
+#define FD_TM_ALIGN_MAX_N 1024
+#define FD_TM_ALIGN_WS_BYTES(P, parts, Na, Nb)                                                                       \
+  ((long)(P) * (long)(parts) * 4L * 32L * 8L + (long)(P) * 4L * 16L * 8L +                                           \
+   (long)(P) * (long)(parts) * 4L * (long)(Na) * (((long)(Nb) + 31L) / 32L) * 8L + (long)(P) * 4L * 2L * (long)(Na) * 2L)
+int fd_tm_align(const float* A, long a_stride, int Na, const float* B, long b_stride, int Nb, const int* ia, const int* ib,
+                const float* mask_a, const float* mask_b, int P, int search_step, int max_dp, int parts, void* ws, double* out,
+                int* map, double* transform, void* stream);
 
 /* ---- secondary structure and the shape columns (se3_diffusion_amd/csrc/fd_dssp.hip) ----
  * Kabsch & Sander (1983) in the order the DSSP program applies it, and the reference's SHAPE_METRICS (analysis/metrics.py:37-42:

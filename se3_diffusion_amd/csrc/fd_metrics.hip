@@ -26,9 +26,12 @@
 // through LDS (fd_optim.hip::block_reduce3's pattern), the search keeps its sums inside the wave.  The results are bitwise
 // reproducible for a given shape, the search's also whatever parts is.
 #include "fd_common.h"
+#include "fd_tm_core.h"
 #include "../../include/fd_hip.h"
 
 namespace {
+
+using namespace fdtm;                            // jacobi4_largest and the superposition search (fd_tm_core.h)
 
 constexpr int MT = 256;
 constexpr int MW = MT / 64;
@@ -201,71 +204,6 @@ __global__ __launch_bounds__(MT) void backbone_metrics_kernel(const float* __res
   }
 }
 
-// Largest eigenvector of the symmetric 4x4 matrix a (destroyed), by cyclic Jacobi rotations; q = (w, x, y, z), unit length.
-__device__ void jacobi4_largest(double (&a)[4][4], double (&q)[4]) {
-  double v[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 50; ++sweep) {
-    double off = 0.0;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) off += fabs(a[p][r]);
-    if (!(off > 0.0)) break;                      // (also leaves on NaN)
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int r = p + 1; r < 4; ++r) {
-        const double apr = a[p][r];
-        const double g = 100.0 * fabs(apr);
-        if (sweep > 3 && fabs(a[p][p]) + g == fabs(a[p][p]) && fabs(a[r][r]) + g == fabs(a[r][r])) {
-          a[p][r] = 0.0;
-          a[r][p] = 0.0;
-          continue;
-        }
-        if (apr == 0.0) continue;
-        const double theta = (a[r][r] - a[p][p]) / (2.0 * apr);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {             // columns p, r of a and of v
-          const double akp = a[k][p], akr = a[k][r];
-          a[k][p] = c * akp - sn * akr;
-          a[k][r] = sn * akp + c * akr;
-          const double vkp = v[k][p], vkr = v[k][r];
-          v[k][p] = c * vkp - sn * vkr;
-          v[k][r] = sn * vkp + c * vkr;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {             // rows p, r of a
-          const double apk = a[p][k], ark = a[r][k];
-          a[p][k] = c * apk - sn * ark;
-          a[r][k] = sn * apk + c * ark;
-        }
-        a[p][r] = 0.0;
-        a[r][p] = 0.0;
-      }
-    }
-  }
-  double best = a[0][0];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] = v[k][0];
-#pragma unroll
-  for (int j = 1; j < 4; ++j) {
-    if (a[j][j] > best) {
-      best = a[j][j];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) q[k] = v[k][j];
-    }
-  }
-  const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) q[k] /= nrm;
-}
-
 __global__ __launch_bounds__(MT) void aligned_rmsd_kernel(const float* __restrict__ A, long a_stride, const float* __restrict__ B,
                                                           long b_stride, const int* __restrict__ ia, const int* __restrict__ ib,
                                                           const float* __restrict__ mask, int N, double* __restrict__ out,
@@ -394,140 +332,7 @@ __global__ __launch_bounds__(MT) void aligned_rmsd_kernel(const float* __restric
 
 // ---- fd_tm_search: the TM-score of a fixed correspondence by superposition search -----------------------------------------------
 constexpr int TM_MAX_N = 2048;                    // 6 fp32 arrays of 2048 = 48 KB static LDS
-constexpr int TM_MAX_WIDEN = 4096;                // cutoff increments of 0.5 A before a selection of < 3 positions is accepted
 constexpr int TM_PART = 16;                       // doubles per wave partial: score, seed, R | t, passes, first score of seed 0
-
-struct TmPts {
-  const float *ax, *ay, *az, *bx, *by, *bz;       // the compacted counting positions, in LDS
-  int L, nj, lane;                                // nj = ceil(L / 64): bit j of a lane's mask stands for position lane + 64 j
-};
-
-// the at most seven fragment lengths L, L/2, L/4, ... (> 4), 4 and the number of starts 0, step, 2 step, ... <= L - len of each.
-// Slot i < 6 holds L >> i while that is above 4 (the lengths only fall, so the first one at or below 4 ends them), slot 6 the
-// closing 4; an unused slot has no starts and so takes no seed number.  Fixed slots: no dynamically indexed writes.
-struct TmSeeds {
-  int len[7], cnt[7], total;
-};
-
-__device__ __forceinline__ TmSeeds tm_seeds(int L, int seed_step) {
-  TmSeeds s;
-  s.total = 0;
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    const int l = i < 6 ? L >> i : 4;
-    const bool used = L >= 4 && (i == 6 || l > 4);
-    s.len[i] = l;
-    s.cnt[i] = used ? (L - l) / seed_step + 1 : 0;
-    s.total += s.cnt[i];
-  }
-  return s;
-}
-
-__device__ __forceinline__ double tm_d0(int L) { return L > 21 ? 1.24 * cbrt((double)L - 15.0) - 1.8 : 0.5; }
-
-// Optimal proper rotation of the selected positions (Horn's quaternion on the centred cross-covariance, as aligned_rmsd_kernel):
-// rt = R | t in every lane.  Every sum is the lane's run in index order, then the butterfly, whose result is the same bits in all
-// 64 lanes -- so the eigenproblem, solved redundantly by every lane, is wave-uniform without a broadcast.
-__device__ void tm_superpose(const TmPts& q, unsigned sel, double (&rt)[12]) {
-  const double n = (double)fd::wave_sum(__builtin_popcount(sel));
-  double c[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int j = 0; j < q.nj; ++j) {
-    if (!((sel >> j) & 1u)) continue;
-    const int k = q.lane + 64 * j;
-    c[0] += (double)q.ax[k];
-    c[1] += (double)q.ay[k];
-    c[2] += (double)q.az[k];
-    c[3] += (double)q.bx[k];
-    c[4] += (double)q.by[k];
-    c[5] += (double)q.bz[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) c[k] = fd::wave_sum(c[k]) / n;
-  double s[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) s[k] = 0.0;
-  for (int j = 0; j < q.nj; ++j) {
-    if (!((sel >> j) & 1u)) continue;
-    const int k = q.lane + 64 * j;
-    const double ax = (double)q.ax[k] - c[0], ay = (double)q.ay[k] - c[1], az = (double)q.az[k] - c[2];
-    const double bx = (double)q.bx[k] - c[3], by = (double)q.by[k] - c[4], bz = (double)q.bz[k] - c[5];
-    s[0] += ax * bx;
-    s[1] += ax * by;
-    s[2] += ax * bz;
-    s[3] += ay * bx;
-    s[4] += ay * by;
-    s[5] += ay * bz;
-    s[6] += az * bx;
-    s[7] += az * by;
-    s[8] += az * bz;
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) s[k] = fd::wave_sum(s[k]);
-  const double Sxx = s[0], Sxy = s[1], Sxz = s[2], Syx = s[3], Syy = s[4], Syz = s[5], Szx = s[6], Szy = s[7], Szz = s[8];
-  double n4[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
-                     {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
-                     {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
-                     {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
-  double qn[4];
-  jacobi4_largest(n4, qn);
-  const double w = qn[0], x = qn[1], y = qn[2], z = qn[3];
-  rt[0] = w * w + x * x - y * y - z * z;
-  rt[1] = 2.0 * (x * y - w * z);
-  rt[2] = 2.0 * (x * z + w * y);
-  rt[3] = 2.0 * (x * y + w * z);
-  rt[4] = w * w - x * x + y * y - z * z;
-  rt[5] = 2.0 * (y * z - w * x);
-  rt[6] = 2.0 * (x * z - w * y);
-  rt[7] = 2.0 * (y * z + w * x);
-  rt[8] = w * w - x * x - y * y + z * z;
-  rt[9] = c[3] - (rt[0] * c[0] + rt[1] * c[1] + rt[2] * c[2]);
-  rt[10] = c[4] - (rt[3] * c[0] + rt[4] * c[1] + rt[5] * c[2]);
-  rt[11] = c[5] - (rt[6] * c[0] + rt[7] * c[1] + rt[8] * c[2]);
-}
-
-// d2 of position k under rt, and the lane's selection bits for a squared cutoff
-__device__ __forceinline__ double tm_d2(const TmPts& q, const double (&rt)[12], int k) {
-  const double ax = (double)q.ax[k], ay = (double)q.ay[k], az = (double)q.az[k];
-  const double dx = (rt[0] * ax + rt[1] * ay + rt[2] * az + rt[9]) - (double)q.bx[k];
-  const double dy = (rt[3] * ax + rt[4] * ay + rt[5] * az + rt[10]) - (double)q.by[k];
-  const double dz = (rt[6] * ax + rt[7] * ay + rt[8] * az + rt[11]) - (double)q.bz[k];
-  return dx * dx + dy * dy + dz * dz;
-}
-
-__device__ __forceinline__ unsigned tm_select(const TmPts& q, const double (&rt)[12], double dc2) {
-  unsigned ns = 0;
-  for (int j = 0; j < q.nj; ++j) {
-    const int k = q.lane + 64 * j;
-    if (k >= q.L) break;
-    if (tm_d2(q, rt, k) < dc2) ns |= 1u << j;
-  }
-  return ns;
-}
-
-// score(R, t, dcut): (1/L) sum 1 / (1 + d2 / d0^2) over all counting positions; *sel (when asked for) = the positions with
-// d2 < dcut^2, dcut widened by 0.5 until at least three are selected.  The widening loop is wave-uniform and bounded
-// (TM_MAX_WIDEN); a score that is not finite (a NaN or infinite coordinate among the counting positions) can never become a
-// candidate, so its selection is not widened at all.
-__device__ double tm_score_pass(const TmPts& q, const double (&rt)[12], double d0sq, double dcut, unsigned* sel) {
-  double sum = 0.0;
-  for (int j = 0; j < q.nj; ++j) {
-    const int k = q.lane + 64 * j;
-    if (k >= q.L) break;
-    sum += 1.0 / (1.0 + tm_d2(q, rt, k) / d0sq);
-  }
-  sum = fd::wave_sum(sum) / (double)q.L;
-  if (!sel) return sum;
-  unsigned ns = tm_select(q, rt, dcut * dcut);
-  int cnt = fd::wave_sum(__builtin_popcount(ns));
-  const bool finite = sum - sum == 0.0;           // (false for NaN and for infinities; the same bits in every lane)
-  for (int widen = 0; finite && cnt < 3 && widen < TM_MAX_WIDEN; ++widen) {
-    dcut += 0.5;
-    ns = tm_select(q, rt, dcut * dcut);
-    cnt = fd::wave_sum(__builtin_popcount(ns));
-  }
-  *sel = ns;
-  return sum;
-}
 
 // Block c of pair p (blockIdx.x = p parts + c) stages the pair's counting positions once; then wave w owns the seeds
 // 4 c + w, + 4 parts, ...  No block barrier after the staging: the seeds take different numbers of refinements.
@@ -604,28 +409,17 @@ __global__ __launch_bounds__(MT, 3) void tm_search_kernel(const float* __restric
   if (L < 4) {
     // no search: the formula under the whole-set superposition (NaN for an empty pair), by the first wave of the first part
     if (c == 0 && wave == 0) {
-      unsigned all = 0;
-      for (int j = 0; j < q.nj; ++j)
-        if (lane + 64 * j < L) all |= 1u << j;
-      tm_superpose(q, all, best_rt);
+      tm_superpose(q, tm_all(q), best_rt);
       best = tm_score_pass(q, best_rt, d0sq, 0.0, nullptr);
       first0 = best;
     }
   } else {
     const TmSeeds sd = tm_seeds(L, seed_step);
     for (int seed = 4 * c + wave; seed < sd.total; seed += 4 * parts) {
-      int rest = seed, start = 0, stop = 0;
-      bool found = false;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        if (!found && rest < sd.cnt[i]) {
-          found = true;
-          start = rest * seed_step;
-          stop = start + sd.len[i];
-        } else if (!found) {
-          rest -= sd.cnt[i];
-        }
-      }
+      int start, stop;
+      tm_seed_range(sd, seed, seed_step, start, stop);
+      // fdtm::tm_run_seed, spelt out: called as that helper the kernel no longer fits the 168 VGPRs of its three-waves bound
+      // (21 spilled; measured with -Rpass-analysis=kernel-resource-usage), spelt out it takes 164 as before
       unsigned sel = 0;
       for (int j = 0; j < q.nj; ++j) {
         const int k = lane + 64 * j;
@@ -637,7 +431,7 @@ __global__ __launch_bounds__(MT, 3) void tm_search_kernel(const float* __restric
       if (seed == 0) first0 = s;
       bool settled = false;
       for (int it = 0;; ++it) {
-        if (s > best) {                           // every call of score is a candidate; strictly greater: the earliest wins
+        if (s > best) {
           best = s;
           best_seed = seed;
 #pragma unroll
@@ -648,7 +442,7 @@ __global__ __launch_bounds__(MT, 3) void tm_search_kernel(const float* __restric
         tm_superpose(q, sel, rt);
         s = tm_score_pass(q, rt, d0sq, d0s + 1.0, &next);
         ++passes;
-        settled = fd::wave_sum(next == sel ? 0 : 1) == 0;      // "selection unchanged": in every lane of the wave
+        settled = fd::wave_sum(next == sel ? 0 : 1) == 0;
         sel = next;
       }
     }

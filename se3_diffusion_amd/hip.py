@@ -287,6 +287,7 @@ _SIGS = {
     "fd_backbone_metrics": "plpiips",
     "fd_aligned_rmsd": "plplpppiipps",
     "fd_tm_search": "plplppp" + "iiiii" + "ppp" + "s",
+    "fd_tm_align": "pliplipppp" + "iiii" + "pppp" + "s",
     "fd_dssp_hbonds": "plppiipps",
     "fd_dssp_assign": "plipppiipps",
 }

@@ -9,10 +9,15 @@ and reports nm), tm_kabsch, the TM-score formula under the one least-squares sup
 of the given correspondence -- and tm_score, that TM-score itself: the maximum over superpositions, found by the seed-and-refine
 search of Zhang & Skolnick's TM-score program (fd_tm_search; the search is spelt out in include/fd_hip.h).  It is the tm_score
 column of the reference (analysis/metrics.py:44-46,104-105) for pairs whose residue-to-residue correspondence is given: sample
-against ground truth, against its refolded self, against another sample of equal length.  What is NOT here is TM-align's search
-over alignments, which the reference's tmtools.tm_align also performs; and agreement with the values tmtools or the TM-score
-program print is not verified, because neither is available to the tests -- they check a float64 restatement of the search and
-its analytic properties.
+against ground truth, against its refolded self, against another sample of equal length.
+
+tm_align / tm_align_matrix: TM-align's search over alignments (fd_tm_align: four initial alignments, a Needleman-Wunsch DP on the
+device, the iteration between DP and superposition search; include/fd_hip.h is the specification and lists the deliberate
+simplifications) -- what the reference's tmtools.tm_align performs for its tm_score column, for chains of any two lengths: sample
+against sample of another length, sample against a chain of a structure library (novelty), the diversity matrix of a mixed-length
+run.  Verified: a float64 restatement of the specification, analytic properties (rigid copies, deletions, identical chains) and
+three pairs of deposited chains.  NOT verified: agreement with the values tmtools or the TM-score program print, for tm_score and
+for tm_align alike, because neither is available to the tests.
 
 secondary_structure: the reference's SHAPE_METRICS (analysis/metrics.py:37-42, :58-69) -- coil_percent, helix_percent,
 strand_percent, non_coil_percent from Kabsch & Sander's assignment (fd_dssp_hbonds, fd_dssp_assign; include/fd_hip.h is the
@@ -37,6 +42,10 @@ RMSD_SLOTS = ("num_aligned", "mean_dist", "rmsd", "tm_kabsch", "reflection", "ma
 TM_SLOTS = ("num_aligned", "tm_score", "tm_kabsch", "best_seed", "num_seeds", "d0", "passes")
 TM_MAX_N = 2048          # fd_tm_search's limit (48 KB of LDS for the six coordinate arrays)
 TM_FILL_BLOCKS = 768     # blocks resident at once on the 256 CUs of an MI355X: three per CU (164 VGPRs, 48 KB of LDS each)
+TM_ALIGN_SLOTS = ("La", "Lb", "num_aligned", "tm_norm_a", "tm_norm_b", "rmsd", "d0_a", "d0_b", "best_class", "num_dp", "num_units",
+                  "search_tm")
+TM_ALIGN_MAX_N = 1024    # FD_TM_ALIGN_MAX_N: both chains of a pair stay in LDS (six fp32 arrays of 1024)
+TM_ALIGN_FILL_BLOCKS = 256    # the seed launch keeps about 100 KB of LDS per block: one block per CU of an MI355X
 SHAPE_SLOTS = ("num_res", "helix_percent", "strand_percent", "coil_percent", "non_coil_percent", "radius_of_gyration",
                "num_hbonds", "overflow")
 SHAPE_COLUMNS = ("coil_percent", "helix_percent", "strand_percent", "non_coil_percent", "radius_of_gyration")    # the reference's names
@@ -299,13 +308,143 @@ def pairwise_tm(pos, mask=None, seed_step=1, max_iter=20):
     return m
 
 
+def tm_align_units(La, Lb):
+    """Number of units fd_tm_align's seed launch deals to its waves for chains of La and Lb counting positions (include/fd_hip.h):
+    the gapless offsets plus the fragment pairs.  0 when the shorter chain has fewer than five."""
+    Lmin = min(La, Lb)
+    if Lmin < 5:
+        return 0
+    m = min(Lmin, max(Lmin // 2, 5))
+    f = min(20, Lmin // 3)
+    units = La + Lb - 2 * m + 1
+    if f >= 4:
+        starts = lambda L: (L - f) // max(f, -(-(L - f + 1) // 8)) + 1
+        units += starts(La) * starts(Lb)
+    return units
+
+
+def tm_align_parts(P, Na, Nb):
+    """How many blocks share the seed units of one pair when the caller does not say: enough for P * parts to reach
+    TM_ALIGN_FILL_BLOCKS when there are few pairs, never more than ceil(units / 4).  From Na and Nb, not from the masks, so nothing
+    is read back; the result does not depend on it bit for bit."""
+    if P <= 0:
+        return 1
+    return max(1, min(-(-tm_align_units(Na, Nb) // 4), -(-TM_ALIGN_FILL_BLOCKS // P)))
+
+
+def tm_align_ws_bytes(P, parts, Na, Nb):
+    """FD_TM_ALIGN_WS_BYTES of include/fd_hip.h"""
+    return P * parts * 4 * 32 * 8 + P * 4 * 16 * 8 + P * parts * 4 * Na * ((Nb + 31) // 32) * 8 + P * 4 * 2 * Na * 2
+
+
+def _d0(L):
+    """d0(L) of include/fd_hip.h on a float64 tensor of lengths"""
+    return torch.where(L > 21, 1.24 * (L - 15.0).clamp_min(0.0).pow(1.0 / 3.0) - 1.8, torch.full_like(L, 0.5))
+
+
+def _align_call(pos_1, pos_2, mask_1, mask_2, ia, ib, P, search_step, max_dp, parts, want_transform):
+    a, a_stride = _points(pos_1)
+    b, b_stride = _points(pos_2)
+    Na, Nb = a.shape[1], b.shape[1]
+    if Na > TM_ALIGN_MAX_N or Nb > TM_ALIGN_MAX_N:
+        raise ValueError(f"tm_align: chains of {Na} and {Nb} positions, at most {TM_ALIGN_MAX_N} are supported")
+    dev = a.device
+    if mask_1 is not None:
+        mask_1 = _f32c(mask_1.reshape(-1, Na))
+    if mask_2 is not None:
+        mask_2 = _f32c(mask_2.reshape(-1, Nb))
+    if parts is None:
+        parts = tm_align_parts(P, Na, Nb)
+    out = torch.empty((P, 16), dtype=torch.float64, device=dev)
+    amap = torch.empty((P, Na), dtype=torch.int32, device=dev)
+    tr = torch.empty((P, 12), dtype=torch.float64, device=dev) if want_transform else None
+    ws = torch.empty((max(8, tm_align_ws_bytes(P, max(1, int(parts)), Na, Nb)) + 7) // 8, dtype=torch.float64, device=dev)
+    hip.get_lib().call("fd_tm_align", a, a_stride, Na, b, b_stride, Nb, ia, ib, mask_1, mask_2, P, search_step, max_dp, parts, ws,
+                       out, amap, tr)
+    if Na == 0 or Nb == 0:
+        # the entry point launches nothing on an empty chain: the lengths, no alignment, NaN in the score slots
+        def lengths(mask, idx, N):
+            if mask is None or N == 0:
+                return torch.full((P,), float(N), dtype=torch.float64, device=dev)
+            rows = (mask != 0).sum(-1).to(torch.float64)
+            return rows[:P] if idx is None else rows[idx.long()]
+        out.zero_()
+        out[:, 0], out[:, 1] = lengths(mask_1, ia, Na), lengths(mask_2, ib, Nb)
+        out[:, 6], out[:, 7] = _d0(out[:, 0]), _d0(out[:, 1])
+        out[:, 8] = -1.0
+        out[:, [3, 4, 5, 11]] = float("nan")
+        amap.fill_(-1)
+        if tr is not None:
+            tr.fill_(float("nan"))
+    return out, amap, tr
+
+
+def tm_align(pos_1, pos_2, mask_1=None, mask_2=None, search_step=40, max_dp=30, return_transform=False, parts=None):
+    """TM-align of pos_1 [P,Na,3] against pos_2 [P,Nb,3] (or the same without P; strided views such as atom37[:, :, 1] are read in
+    place): the search over residue-to-residue alignments that include/fd_hip.h specifies (fd_tm_align), for chains of any two
+    lengths.  mask_1 [P,Na], mask_2 [P,Nb]: the positions that count.  search_step: distance between the seed fragments of the
+    search phase; max_dp: DP iterations per gap penalty; parts: blocks per pair of the seed launch (None: tm_align_parts; the
+    result does not depend on it bit for bit).  dict name -> float64 device tensor [P] (0-d without P) under TM_ALIGN_SLOTS --
+    tm_norm_b is the reference's tm_score column when pos_2 is the ground truth -- plus map (int32 [P,Na]: for each position of
+    pos_1 its partner in pos_2, or -1); return_transform adds R [P,3,3] and t [P,3] of tm_norm_b's superposition, aligned = R a + t.
+    Agreement with tmtools is NOT verified (see the module docstring).  Na, Nb <= 1024, or ValueError before anything is launched.
+    Three launches, no host synchronisation."""
+    batched = pos_1.dim() == 3
+    if not batched:
+        pos_1, pos_2 = pos_1[None], pos_2[None]
+        mask_1 = None if mask_1 is None else mask_1[None]
+        mask_2 = None if mask_2 is None else mask_2[None]
+    if pos_1.dim() != 3 or pos_2.dim() != 3 or pos_1.shape[0] != pos_2.shape[0]:
+        raise ValueError(f"point sets of shapes {tuple(pos_1.shape)} and {tuple(pos_2.shape)}")
+    P = pos_1.shape[0]
+    out, amap, tr = _align_call(pos_1, pos_2, mask_1, mask_2, None, None, P, search_step, max_dp, parts, return_transform)
+    pick = (lambda x: x) if batched else (lambda x: x[0])
+    res = {name: pick(out[:, k]) for k, name in enumerate(TM_ALIGN_SLOTS)}
+    res["map"] = pick(amap)
+    if return_transform:
+        res["R"] = pick(tr[:, :9].reshape(P, 3, 3))
+        res["t"] = pick(tr[:, 9:])
+    return res
+
+
+def tm_align_matrix(pos_a, mask_a=None, pos_b=None, mask_b=None, search_step=40, max_dp=30, parts=None):
+    """TM-align of every set of pos_a [Ma,Na,3] (mask_a [Ma,Na]: padding) against every set of pos_b [Mb,Nb,3]: dict of float64
+    [Ma,Mb] device tensors tm_norm_a (normalised by the length of the row's chain) and tm_norm_b (by the column's) -- samples
+    against a structure library for novelty.  With pos_b=None it is the mixed-length diversity matrix of one set: the upper pairs
+    i < j are run (set i onto set j) and mirrored with the two normalisations swapped, so tm_norm_a[j, i] = tm_norm_b[i, j]; the
+    diagonal is 1.  One call of fd_tm_align over all pairs."""
+    if pos_a.dim() != 3 or (pos_b is not None and pos_b.dim() != 3):
+        raise ValueError("tm_align_matrix: expected [M,N,3] point sets")
+    dev = pos_a.device
+    Ma = pos_a.shape[0]
+    if pos_b is None:
+        iu = torch.triu_indices(Ma, Ma, 1, device=dev)
+        ia, ib = iu[0].to(torch.int32).contiguous(), iu[1].to(torch.int32).contiguous()
+        out, _, _ = _align_call(pos_a, pos_a, mask_a, mask_a, ia, ib, ia.numel(), search_step, max_dp, parts, False)
+        res = {}
+        for name, other in (("tm_norm_a", "tm_norm_b"), ("tm_norm_b", "tm_norm_a")):
+            m = torch.zeros((Ma, Ma), dtype=torch.float64, device=dev)
+            m[iu[0], iu[1]] = out[:, TM_ALIGN_SLOTS.index(name)]
+            m[iu[1], iu[0]] = out[:, TM_ALIGN_SLOTS.index(other)]
+            m.fill_diagonal_(1.0)
+            res[name] = m
+        return res
+    Mb = pos_b.shape[0]
+    ia = torch.arange(Ma, device=dev, dtype=torch.int32).repeat_interleave(Mb).contiguous()
+    ib = torch.arange(Mb, device=dev, dtype=torch.int32).repeat(Ma).contiguous()
+    out, _, _ = _align_call(pos_a, pos_b, mask_a, mask_b, ia, ib, Ma * Mb, search_step, max_dp, parts, False)
+    return {name: out[:, TM_ALIGN_SLOTS.index(name)].reshape(Ma, Mb) for name in ("tm_norm_a", "tm_norm_b")}
+
+
 def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape=False):
     """One dict of Python floats per backbone with the reference's column names (Experiment.eval_fn,
     experiments/train_se3_diffusion.py:475-508, and CA_VIOLATION_METRICS): ca_ca_bond_dev, ca_ca_valid_percent,
     ca_steric_clash_percent, num_ca_steric_clashes, num_res, fixed_residues, diffused_percentage -- and this module's own
     BACKBONE_SLOTS.  gt_atom37 adds aligned_rmsd_to_gt (calc_aligned_rmsd of the sample's CA onto the ground truth's) over the
     diffused present residues (analysis/metrics.py:100-102); with tm=True it also adds tm_score_to_gt, tm_score over the same
-    residues, normalised by their number -- the ground truth's length under the reference's own masking (metrics.py:100-105).
+    residues, normalised by their number -- the ground truth's length under the reference's own masking (metrics.py:100-105);
+    with tm="align" it adds tm_align_to_gt instead: tm_align's tm_norm_b of the sample's CA against the ground truth's over the same
+    residues, the alignment search protein_metrics itself runs (tmtools.tm_align; agreement with its values is not verified).
     shape=True adds the reference's SHAPE_METRICS and non_coil_percent (SHAPE_COLUMNS; secondary_structure without a proline
     mask, as the backbone carries no sequence).  One device-to-host copy."""
     B, N = atom37.shape[:2]
@@ -318,7 +457,11 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape
         diffused = (1.0 - fixed) * (res_mask != 0)
         out, _ = _rmsd_call(a37[:, :, CA], g37[:, :, CA], diffused, None, None, B, False)
         cols.append(out)
-        if tm:
+        if isinstance(tm, str):
+            if tm != "align":
+                raise ValueError(f"eval_rows: tm = {tm!r}, expected False, True or 'align'")
+            cols.append(_align_call(a37[:, :, CA], g37[:, :, CA], diffused, diffused, None, None, B, 40, 30, None, False)[0])
+        elif tm:
             cols.append(_tm_call(a37[:, :, CA], g37[:, :, CA], diffused, None, None, B, 1, 20, None, False)[0])
     if shape:
         shape_at = sum(c.shape[1] for c in cols)
@@ -333,7 +476,9 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape
         row["diffused_percentage"] = (n - v[12]) / n if n else float("nan")
         if gt_atom37 is not None:
             row["aligned_rmsd_to_gt"] = v[13 + RMSD_SLOTS.index("mean_dist")]
-            if tm:
+            if isinstance(tm, str):
+                row["tm_align_to_gt"] = v[21 + TM_ALIGN_SLOTS.index("tm_norm_b")]
+            elif tm:
                 row["tm_score_to_gt"] = v[21 + TM_SLOTS.index("tm_score")]
         if shape:
             row.update({name: v[shape_at + SHAPE_SLOTS.index(name)] for name in SHAPE_COLUMNS})

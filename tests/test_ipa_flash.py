@@ -2,7 +2,8 @@
 |o_pt|, o_pair) -- against (1) the launch sequence it replaces (q k^T GEMM -> fd_ipa_attn_fwd -> a v / a v_pts GEMMs ->
 fd_ipa_opt_fwd; the point and o_pt kernels have their own float64 test in test_frames.py) and (2) a float64 restatement of
 the reference's arithmetic on the same inputs.  Tolerances are relative to each output group's maximum and <= 10 x what the
-kernel achieves (recorded by parity_log)."""
+kernel achieves (recorded by parity_log).  The backward below is compared with the launch sequence it replaces; that sequence, and
+every other launch path of the backward, is itself checked against float64 autograd in test_ipa_bwd.py."""
 import math
 
 import pytest

@@ -34,12 +34,12 @@ __device__ __forceinline__ f32x4 mfma_16x16x32_bf16(uint4 a, uint4 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(fd_bf16x8, a), __builtin_bit_cast(fd_bf16x8, b), c, 0, 0, 0);
 }
 // two f32 -> one dword of two bf16, round-to-nearest-even (v_cvt_pk_bf16_f32): lo in bits 0..15
+typedef float fd_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  // (asm rather than two __bf16 casts: the compiler otherwise re-derives each half with its own conversion when
-  // the packed word is unpacked again by the split code)
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
+  // (a vector conversion, not an asm statement: the compiler pads the VALU write -> MFMA operand wait states only for
+  //  instructions it sees, and the register splits of fd_gemm_w.h / fd_chain.h feed MFMAs directly)
+  const fd_f32x2 v = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, fd_bf16x2));
 }
 __device__ __forceinline__ float bf16lo_f32(unsigned w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bf16hi_f32(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }

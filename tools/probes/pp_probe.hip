@@ -23,10 +23,12 @@ constexpr int PIECE = 1024, UNIT = 12 * PIECE, NUNITS = 128;
 __device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  unsigned r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
+  // (as csrc/gfx950/fd_intrin.h: a conversion the compiler sees, so that it keeps the wait states in front of the MFMAs)
+  const f32x2 v = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
 __device__ __forceinline__ void split8(const float (&x)[8], uint4& s0, uint4& s1, uint4& s2) {
   unsigned t0[4], t1[4], t2[4];

@@ -7,8 +7,10 @@
 // in "chained" k order (slot (g, e') <-> k = k0 + 16 (e' >> 2) + 4 g + (e' & 3)); operands that come from memory use
 // the "natural" order k = k0 + 8 g + e'.  Weights are pre-split into three bf16 planes and packed as units of
 // [4 n-blocks of 16][3 planes][64 lanes] x 16 B (12 KB, one 32-k step) in consumption order; stages of four units
-// stream through a two-stage LDS ring by LDS-DMA.
+// stream through a two-stage LDS ring by LDS-DMA.  The split of an activation fragment (fd_split8) and the order of the six
+// plane products are fd_split.h's.
 #pragma once
+#include "fd_split.h"
 
 #ifndef EM_WAVES
 #define EM_WAVES 4                         // waves per block (8 or 4); a stage holds EM_WAVES / 2 units so that every wave
@@ -24,25 +26,7 @@ constexpr int EM_BLOCKS_PER_CU = 8 / EM_WAVES;
 constexpr int EM_PPW = 12 * EM_UPS / EM_WAVES;   // 1 KB LDS-DMA pieces of a stage per wave: 6 (4 waves x 2 units) or 3 (8 waves x 2 units)
 static_assert(EM_PPW * EM_WAVES == 12 * EM_UPS && (EM_PPW == 6 || EM_PPW == 3), "a stage must split into 3 or 6 whole pieces per wave");
 
-__device__ __forceinline__ void em_split8(const float (&x)[8], uint4& s0, uint4& s1, uint4& s2) {
-  unsigned t0[4], t1[4], t2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float u = x[2 * j], v = x[2 * j + 1];
-    const unsigned hh = fd::pack_bf16(u, v);
-    const float ru = u - fd::bf16lo_f32(hh), rv = v - fd::bf16hi_f32(hh);
-    const unsigned mm = fd::pack_bf16(ru, rv);
-    const float qu = ru - fd::bf16lo_f32(mm), qv = rv - fd::bf16hi_f32(mm);
-    t0[j] = hh;
-    t1[j] = mm;
-    t2[j] = fd::pack_bf16(qu, qv);
-  }
-  s0 = make_uint4(t0[0], t0[1], t0[2], t0[3]);
-  s1 = make_uint4(t1[0], t1[1], t1[2], t1[3]);
-  s2 = make_uint4(t2[0], t2[1], t2[2], t2[3]);
-}
-
-
+// two accumulator blocks of a row (units 16 nb + 4 g + r, nb consecutive) -> the three planes of the next layer's 32-k fragment
 __device__ __forceinline__ void em16_split2(const f32x4& lo, const f32x4& hi, uint4& s0, uint4& s1, uint4& s2) {
   float t[8];
 #pragma unroll
@@ -50,7 +34,7 @@ __device__ __forceinline__ void em16_split2(const f32x4& lo, const f32x4& hi, ui
     t[e] = lo[e];
     t[4 + e] = hi[e];
   }
-  em_split8(t, s0, s1, s2);
+  fd_split8(t, s0, s1, s2);
 }
 
 // half a unit (2 n-blocks x one 32-k step: 6 fragments, 12 MFMAs): the stage loop reads half-unit i + 1 while half-unit i
@@ -66,12 +50,11 @@ __device__ __forceinline__ void em16_read_half(Em16Half& f, const char* __restri
     for (int s = 0; s < 3; ++s) f.w[i][s] = *reinterpret_cast<const uint4*>(u + (i * 3 + s) * EM_PIECE);
 }
 __device__ __forceinline__ void em16_mma_half(f32x4& a0, f32x4& a1, const Em16Half& f, const uint4 (&b)[3]) {
-  constexpr int PW[6] = {2, 1, 0, 1, 0, 0};
-  constexpr int PX[6] = {0, 1, 2, 0, 1, 0};
+  // the six products in fd_split.h's order: the weights are the A side, the activations the B side
 #pragma unroll
   for (int p = 0; p < 6; ++p) {
-    a0 = fd::mfma_16x16x32_bf16(f.w[0][PW[p]], b[PX[p]], a0);
-    a1 = fd::mfma_16x16x32_bf16(f.w[1][PW[p]], b[PX[p]], a1);
+    a0 = fd::mfma_16x16x32_bf16(f.w[0][FD_PA[p]], b[FD_PB[p]], a0);
+    a1 = fd::mfma_16x16x32_bf16(f.w[1][FD_PA[p]], b[FD_PB[p]], a1);
   }
 }
 

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void edge_embed_pack_kernel(const float* __res
     }
   }
   uint4 s0, s1, s2;
-  em_split8(x, s0, s1, s2);
+  fd_split8(x, s0, s1, s2);
   char* dst = img + (long)u * EM_UNIT + (i * 3) * EM_PIECE + lane * 16;
   *reinterpret_cast<uint4*>(dst) = s0;
   *reinterpret_cast<uint4*>(dst + EM_PIECE) = s1;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void edge_embed_pack_zb_kernel(const float* __
     x[e] = n < EE_ZB ? W40[n * EE_C + k] : 0.f;
   }
   uint4 s0, s1, s2;
-  em_split8(x, s0, s1, s2);
+  fd_split8(x, s0, s1, s2);
   char* dst = img + (long)(EE_UNITS + ks) * EM_UNIT + (i * 3) * EM_PIECE + lane * 16;
   *reinterpret_cast<uint4*>(dst) = s0;
   *reinterpret_cast<uint4*>(dst + EM_PIECE) = s1;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64 * EM_WAVES, 2) void edge_embed_kernel(FdEdgeEmbe
         if (hh + 1 < 2 * EM_UPS) em16_read_half(H[(hh + 1) & 1], st + (hh + 1) * (EM_UNIT / 2));
         EM_PIN_MID();
         if (g2 == 0 && (hh & 1) == 0) {
-          if ((r >> 1) == 0) em_split8(x0, b[0], b[1], b[2]); else em_split8(x1, b[0], b[1], b[2]);
+          if ((r >> 1) == 0) fd_split8(x0, b[0], b[1], b[2]); else fd_split8(x1, b[0], b[1], b[2]);
         }
         em16_mma_half(acc1[a], acc1[a + 1], H[hh & 1], b);
         EM_GROUPS(hh + 1 < 2 * EM_UPS);

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void edge_embed_bwd_pack_kernel(const float* _
     x[e] = W[k * EB_C + n];
   }
   uint4 s0, s1, s2;
-  em_split8(x, s0, s1, s2);
+  fd_split8(x, s0, s1, s2);
   char* dst = img + (long)u * EM_UNIT + (i * 3) * EM_PIECE + lane * 16;
   *reinterpret_cast<uint4*>(dst) = s0;
   *reinterpret_cast<uint4*>(dst + EM_PIECE) = s1;

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void edge_mlp_pack16_kernel(EmMat A1, EmMat A2
     x[e] = M.p[(long)n * M.rs + (long)k * M.cs];
   }
   uint4 s0, s1, s2;
-  em_split8(x, s0, s1, s2);
+  fd_split8(x, s0, s1, s2);
   char* dst = img + (long)u * EM_UNIT + (i * 3) * EM_PIECE + lane * 16;
   *reinterpret_cast<uint4*>(dst) = s0;
   *reinterpret_cast<uint4*>(dst + EM_PIECE) = s1;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void edge_mlp_pack_zb_kernel(const float* __re
     x[e] = n < EM_ZB ? W40[n * EM_C + k] : 0.f;
   }
   uint4 s0, s1, s2;
-  em_split8(x, s0, s1, s2);
+  fd_split8(x, s0, s1, s2);
   char* dst = img + (long)(EM_UNITS + ks) * EM_UNIT + (i * 3) * EM_PIECE + lane * 16;
   *reinterpret_cast<uint4*>(dst) = s0;
   *reinterpret_cast<uint4*>(dst + EM_PIECE) = s1;
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void edge_mlp_pack_zbw_kernel(const float* __r
     x[e] = k < EM_ZB ? W40[k * EM_C + n] : 0.f;
   }
   uint4 s0, s1, s2;
-  em_split8(x, s0, s1, s2);
+  fd_split8(x, s0, s1, s2);
   char* dst = img + (long)u * EM_UNIT + (i * 3) * EM_PIECE + lane * 16;
   *reinterpret_cast<uint4*>(dst) = s0;
   *reinterpret_cast<uint4*>(dst + EM_PIECE) = s1;
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(64 * EM_WAVES, 2) void edge_mlp16_kernel(FdEdgeMlpD
             const int r = EM_UPS * sg + (hh >> 1), g2 = r & 1, a = 4 * g2 + 2 * (hh & 1);
             EM_PIN_TOP();
             if (hh + 1 < 2 * EM_UPS) em16_read_half(Hz[(hh + 1) & 1], st + (hh + 1) * (EM_UNIT / 2));
-            if (g2 == 0 && (hh & 1) == 0) em_split8(kz[r >> 1], bz[0], bz[1], bz[2]);
+            if (g2 == 0 && (hh & 1) == 0) fd_split8(kz[r >> 1], bz[0], bz[1], bz[2]);
             em16_mma_half(X[a], X[a + 1], Hz[hh & 1], bz);
             EM_GROUPS(hh + 1 < 2 * EM_UPS);
             if (hh == 1) stage_prefetch();

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(512, 1) void edge_mlp_pair_kernel(FdEdgeMlpDesc d) 
       for (int ks = 0; ks < 4; ++ks) {
         float t[8] = {xv[2 * ks].x, xv[2 * ks].y, xv[2 * ks].z, xv[2 * ks].w,
                       xv[2 * ks + 1].x, xv[2 * ks + 1].y, xv[2 * ks + 1].z, xv[2 * ks + 1].w};
-        em_split8(t, Xb[ks][0], Xb[ks][1], Xb[ks][2]);
+        fd_split8(t, Xb[ks][0], Xb[ks][1], Xb[ks][2]);
       }
     }
 

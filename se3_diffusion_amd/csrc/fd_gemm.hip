@@ -483,6 +483,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
   }
 }
 
+#include "fd_split.h"        // the split-bf16 arithmetic of tiles 4 / 6 / 10 / 12 / 13 / 14: fp32 -> 3 bf16 planes, the six products
 #include "fd_gemm_split.h"   // gemm_bx3_kernel: tile code 4
 #include "fd_gemm_direct.h"  // gemm_direct_kernel: tile code 5
 

@@ -1,6 +1,6 @@
 // 64 x 64 split-bf16 GEMM kernel (fd_gemm tile code 10) for the node-level and attention GEMMs: M = B*N rows of a few
 // thousand, N_out / K of a few hundred, 100..1000 blocks per launch.  Included by fd_gemm.hip inside its anonymous
-// namespace (uses GemmArgs, store_tile, store_tile_vec).
+// namespace (uses GemmArgs, store_tile, store_tile_vec; the split and the product order are fd_split.h's).
 //
 // These launches ran on the 64 x 64 fp32-MFMA kernel (tile 2): one 32 x 32 wave tile costs 16 v_mfma_f32_32x32x2_f32
 // = 1024 matrix-pipe cycles per 32 k.  Here the same wave tile costs 12 v_mfma_f32_32x32x16_bf16 = 384 cycles (fp32
@@ -25,18 +25,6 @@ constexpr int S_STAGE = 2 * S_OP_BYTES;
 constexpr int S_LDS = 2 * S_STAGE;                    // 57,600 B: two blocks per CU
 static_assert(3 * S_TR_PLANE <= S_OP_BYTES, "operand image");
 static_assert(64 * (64 + 4) * 4 <= S_LDS, "epilogue scratch");
-
-__device__ __forceinline__ void s64_split4(const float4 v, uint2& s0, uint2& s1, uint2& s2) {
-  const unsigned h0 = fd::pack_bf16(v.x, v.y), h1 = fd::pack_bf16(v.z, v.w);
-  const float r0 = v.x - fd::bf16lo_f32(h0), r1 = v.y - fd::bf16hi_f32(h0);
-  const float r2 = v.z - fd::bf16lo_f32(h1), r3 = v.w - fd::bf16hi_f32(h1);
-  const unsigned m0 = fd::pack_bf16(r0, r1), m1 = fd::pack_bf16(r2, r3);
-  const float q0 = r0 - fd::bf16lo_f32(m0), q1 = r1 - fd::bf16hi_f32(m0);
-  const float q2 = r2 - fd::bf16lo_f32(m1), q3 = r3 - fd::bf16hi_f32(m1);
-  s0 = make_uint2(h0, h1);
-  s1 = make_uint2(m0, m1);
-  s2 = make_uint2(fd::pack_bf16(q0, q1), fd::pack_bf16(q2, q3));
-}
 
 // One 64-row operand of a 32-k stage.  `rs` = stride of the row index (m of A, n of B), `ks` = stride of k.
 template <bool KC>
@@ -82,7 +70,7 @@ struct S64Stager {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       uint2 s0, s1, s2;
-      s64_split4(r[i], s0, s1, s2);
+      fd_split4(r[i], s0, s1, s2);
       constexpr int PL = KC ? 32 : S_TR_PLANE;
       *reinterpret_cast<uint2*>(img + wofs[i]) = s0;
       *reinterpret_cast<uint2*>(img + wofs[i] + PL) = s1;
@@ -169,16 +157,10 @@ __global__ __launch_bounds__(256, 2) void gemm_s64_kernel(GemmArgs g) {
   auto mma = [&](const char* st) __attribute__((always_inline)) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      uint4 fa[3], fb[3];
-      s64_frag<A_KC>(fa, st, wm, s, lane);
-      s64_frag<B_KC>(fb, st + S_OP_BYTES, wn, s, lane);
-      // the six products with i + j <= 2, small terms first
-      acc[0][0] = fd::mfma_32x32x16_bf16(fa[2], fb[0], acc[0][0]);
-      acc[0][0] = fd::mfma_32x32x16_bf16(fa[1], fb[1], acc[0][0]);
-      acc[0][0] = fd::mfma_32x32x16_bf16(fa[0], fb[2], acc[0][0]);
-      acc[0][0] = fd::mfma_32x32x16_bf16(fa[1], fb[0], acc[0][0]);
-      acc[0][0] = fd::mfma_32x32x16_bf16(fa[0], fb[1], acc[0][0]);
-      acc[0][0] = fd::mfma_32x32x16_bf16(fa[0], fb[0], acc[0][0]);
+      uint4 fa[1][3], fb[1][3];
+      s64_frag<A_KC>(fa[0], st, wm, s, lane);
+      s64_frag<B_KC>(fb[0], st + S_OP_BYTES, wn, s, lane);
+      fd_mma6<false, 1, 1>(acc, fa, fb);
     }
   };
 

@@ -1,5 +1,6 @@
 // Split-bf16 GEMM kernel (fd_gemm tile codes 4 and 6) for the pair-level GEMMs.  Included by fd_gemm.hip inside its
-// anonymous namespace (uses GemmArgs, store_tile, store_tile_vec, fd_xcd_swizzle).
+// anonymous namespace (uses GemmArgs, store_tile, store_tile_vec, fd_xcd_swizzle; the split fd_split8 and the six-product
+// order fd_mma6 are fd_split.h's, shared with every other split-bf16 kernel).
 //
 // gfx950 runs the bf16 MFMA at 16x the fp32-MFMA rate.  An fp32 value splits EXACTLY into three bf16 terms
 // x = x0 + x1 + x2 (round-to-nearest at every stage: 3 x (8 bits + sign of the next residual) covers the 24-bit
@@ -133,24 +134,6 @@ __device__ __forceinline__ void store_tile_t(const FdGemmDesc& d, float* __restr
   }
 }
 
-__device__ __forceinline__ void split8(const float (&x)[8], uint4& s0, uint4& s1, uint4& s2) {
-  unsigned t0[4], t1[4], t2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float u = x[2 * j], v = x[2 * j + 1];
-    const unsigned h = fd::pack_bf16(u, v);
-    const float ru = u - fd::bf16lo_f32(h), rv = v - fd::bf16hi_f32(h);
-    const unsigned m = fd::pack_bf16(ru, rv);
-    const float qu = ru - fd::bf16lo_f32(m), qv = rv - fd::bf16hi_f32(m);
-    t0[j] = h;
-    t1[j] = m;
-    t2[j] = fd::pack_bf16(qu, qv);
-  }
-  s0 = make_uint4(t0[0], t0[1], t0[2], t0[3]);
-  s1 = make_uint4(t1[0], t1[1], t1[2], t1[3]);
-  s2 = make_uint4(t2[0], t2[1], t2[2], t2[3]);
-}
-
 // Stages a ROWS x 16 operand tile with NPROD producer threads.  A slot = (row, group of 8 consecutive k).
 //   KC : k contiguous in memory   -> 2 x float4 per slot, 2 lanes per row
 //   !KC: row contiguous in memory -> 8 dword loads per slot (coalesced across the lanes = rows)
@@ -244,7 +227,7 @@ struct SplitStager {
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       uint4 s0, s1, s2;
-      split8(r[i], s0, s1, s2);
+      fd_split8(r[i], s0, s1, s2);
       *reinterpret_cast<uint4*>(lds + lofs[i]) = s0;
       *reinterpret_cast<uint4*>(lds + lofs[i] + 2 * XBK) = s1;
       *reinterpret_cast<uint4*>(lds + lofs[i] + 4 * XBK) = s2;
@@ -252,13 +235,103 @@ struct SplitStager {
   }
 };
 
+// ---- the pieces of a block that the fresh-block kernel and the persistent kernel below share ----
+// (state -- stagers, ring slots, fragment offsets -- stays in the kernels' own locals and is passed by reference)
+
+// NSET register sets = NSET stages of global loads in flight per producer thread (stage s lives in set s % NSET).
+// (Four sets were measured on the HBM-streamed pair tensor: no change against two -- 1.06 ms on the K = 384
+// edge shape either way -- so the load latency is not what separates it from an L2-resident operand.)
+constexpr int XNSET = 2;
+
+// producer: one loaded register set -> (split) -> ring slot wbuf (the slot of the next LDS store, advanced here)
+template <int BM, class StagerA, class StagerB>
+__device__ __forceinline__ void split_put(const StagerA& sa, const StagerB& sb, char* lds, int& wbuf,
+                                          const float (&xa)[StagerA::NS][8], const float (&xb)[StagerB::NS][8]) {
+  char* dst = lds + wbuf * SplitCfg<BM>::STAGE;
+  sa.store(xa, dst);
+  sb.store(xb, dst + BM * XROWB);
+  wbuf = (wbuf == SplitCfg<BM>::RING - 1) ? 0 : wbuf + 1;
+}
+
+// producer: feeds a sequence of n stages to the consumers, one barrier per stage.  issue(xa, xb) loads the NEXT stage
+// of the sequence into a register set (what differs between the kernels: a fixed tile against a stream of tiles),
+// put(xa, xb) moves a loaded set into the ring (split_put, or more on the way).
+template <int RING, int NSA, int NSB, class Issue, class Put>
+__device__ __forceinline__ void split_pump(int n, float (&ra)[XNSET][NSA][8], float (&rb)[XNSET][NSB][8], Issue& issue,
+                                           Put& put) {
+  constexpr int NSET = XNSET;
+  // AHEAD = how many stages beyond the one being multiplied are complete in LDS at a barrier
+  constexpr int AHEAD = RING - 1;
+#pragma unroll
+  for (int u = 0; u < NSET; ++u)
+    if (u < n) issue(ra[u], rb[u]);
+#pragma unroll
+  for (int u = 0; u < AHEAD; ++u)
+    if (u < n) {
+      put(ra[u], rb[u]);
+      if (u + NSET < n) issue(ra[u], rb[u]);
+    }
+  __syncthreads();   // the first AHEAD stages are in the ring
+  // during stage `it`: stage it+AHEAD goes registers -> its ring slot (last read AHEAD barriers ago) and the loads
+  // of stage it+AHEAD+NSET refill the register set
+  auto step = [&](int it, float (&xa)[NSA][8], float (&xb)[NSB][8]) {
+    if (it + AHEAD < n) {
+      put(xa, xb);
+      if (it + AHEAD + NSET < n) issue(xa, xb);
+    }
+    __syncthreads();
+  };
+  for (int it = 0; it < n; it += NSET) {
+#pragma unroll
+    for (int u = 0; u < NSET; ++u)
+      if (it + u < n) step(it + u, ra[(AHEAD + u) % NSET], rb[(AHEAD + u) % NSET]);
+  }
+}
+
+// consumer: the 2 x 2 fragments of ring slot rbuf (the slot of the next fragment read, advanced here).  a_frag / b_frag =
+// per-lane fragment base: row (l31); lane-half h takes k 8h..8h+7 of the 16-k MFMA step
+template <int BM>
+__device__ __forceinline__ void split_read_frags(const char* lds, int& rbuf, int a_frag, int b_frag, uint4 (&xa)[2][3],
+                                                 uint4 (&xb)[2][3]) {
+  const char* st = lds + rbuf * SplitCfg<BM>::STAGE;
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      xa[i][s] = *reinterpret_cast<const uint4*>(st + a_frag + i * 32 * XROWB + s * 2 * XBK);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      xb[j][s] = *reinterpret_cast<const uint4*>(st + b_frag + j * 32 * XROWB + s * 2 * XBK);
+  }
+  rbuf = (rbuf == SplitCfg<BM>::RING - 1) ? 0 : rbuf + 1;
+}
+
+// consumer, ring of three, nk stages: stage it is multiplied out of registers (fd_mma6: the four accumulators interleaved,
+// dependent MFMAs four issues apart) while the fragments of stage it+1 (complete in the ring since the last barrier) are
+// fetched; the barrier itself carries no LDS wait on this side
+template <int BM, bool TRANS>
+__device__ __forceinline__ void split_multiply3(f32x16 (&acc)[2][2], int nk, const char* lds, int& rbuf, int a_frag,
+                                                int b_frag) {
+  uint4 fa[2][2][3], fb[2][2][3];
+  auto step = [&](int it, uint4 (&ca)[2][3], uint4 (&cb)[2][3], uint4 (&na)[2][3], uint4 (&nb)[2][3]) {
+    if (it + 1 < nk) split_read_frags<BM>(lds, rbuf, a_frag, b_frag, na, nb);
+    fd_mma6<TRANS, 2, 2>(acc, ca, cb);
+    fd::block_barrier_nofence();
+  };
+  split_read_frags<BM>(lds, rbuf, a_frag, b_frag, fa[0], fb[0]);
+  for (int it = 0; it < nk; it += 2) {
+    step(it, fa[0], fb[0], fa[1], fb[1]);
+    if (it + 1 < nk) step(it + 1, fa[1], fb[1], fa[0], fb[0]);
+  }
+}
+
 // TRANS: transposed accumulation + LDS-free float4 epilogue (needs ksplit == 1: its split-K atomics would touch one
 // cache line per lane); !TRANS: row-major accumulation, LDS-transposed epilogue or split-K atomics.
 template <int BM, bool A_KC, bool B_KC, bool TRANS>
 __global__ __launch_bounds__(SplitCfg<BM>::NTHR, SplitCfg<BM>::BLOCKS_PER_CU) void gemm_bx3_kernel(GemmArgs g) {
   using Cfg = SplitCfg<BM>;
   constexpr int BN = XBN, TM = 2, TN = 2;
-  constexpr int NCONS = Cfg::NCONS, NPROD = Cfg::NPROD, STAGE = Cfg::STAGE, RING = Cfg::RING;
+  constexpr int NCONS = Cfg::NCONS, NPROD = Cfg::NPROD, RING = Cfg::RING;
   constexpr int A_BYTES = BM * XROWB;
   __shared__ __attribute__((aligned(16))) char lds[Cfg::LDS];
 
@@ -290,11 +363,7 @@ __global__ __launch_bounds__(SplitCfg<BM>::NTHR, SplitCfg<BM>::BLOCKS_PER_CU) vo
     SplitStager<BM, A_KC, NPROD> sa;
     SplitStager<BN, B_KC, NPROD> sb;
     constexpr int NSA = SplitStager<BM, A_KC, NPROD>::NS, NSB = SplitStager<BN, B_KC, NPROD>::NS;
-    // NSET register sets = NSET stages of global loads in flight per producer thread (stage s lives in set s % NSET).
-    // (Four sets were measured on the HBM-streamed pair tensor: no change against two -- 1.06 ms on the K = 384
-    // edge shape either way -- so the load latency is not what separates it from an L2-resident operand.)
-    constexpr int NSET = 2;
-    float ra[NSET][NSA][8], rb[NSET][NSB][8];
+    float ra[XNSET][NSA][8], rb[XNSET][NSB][8];
     sa.init(A, d.a_rs, d.a_cs, m0, d.M, kt0 * XBK, ptid);
     sb.init(B, d.b_cs, d.b_rs, n0, d.N, kt0 * XBK, ptid);   // the staged "row" of B is n
     int lk = kt0;   // stage of the next global load
@@ -307,44 +376,16 @@ __global__ __launch_bounds__(SplitCfg<BM>::NTHR, SplitCfg<BM>::BLOCKS_PER_CU) vo
     // its slots, NPROD == BM): row sums of A over k, taken from the registers on their way to LDS
     const bool do_rowsum = !A_KC && d.a_rowsum != nullptr && bn == 0 && z == 0;
     float rsum = 0.f;
-    int wbuf = 0;   // ring slot of the next LDS store
+    int wbuf = 0;
     auto put = [&](float (&xa)[NSA][8], float (&xb)[NSB][8]) {
       if (!A_KC && do_rowsum) {
 #pragma unroll
         for (int i = 0; i < NSA; ++i)
           rsum += ((xa[i][0] + xa[i][1]) + (xa[i][2] + xa[i][3])) + ((xa[i][4] + xa[i][5]) + (xa[i][6] + xa[i][7]));
       }
-      char* dst = lds + wbuf * STAGE;
-      sa.store(xa, dst);
-      sb.store(xb, dst + A_BYTES);
-      wbuf = (wbuf == RING - 1) ? 0 : wbuf + 1;
+      split_put<BM>(sa, sb, lds, wbuf, xa, xb);
     };
-    // AHEAD = how many stages beyond the one being multiplied are complete in LDS at a barrier
-    constexpr int AHEAD = RING - 1;
-#pragma unroll
-    for (int u = 0; u < NSET; ++u)
-      if (u < nk) issue(ra[u], rb[u]);
-#pragma unroll
-    for (int u = 0; u < AHEAD; ++u)
-      if (u < nk) {
-        put(ra[u], rb[u]);
-        if (u + NSET < nk) issue(ra[u], rb[u]);
-      }
-    __syncthreads();   // the first AHEAD stages are in the ring
-    // during stage `it`: stage it+AHEAD goes registers -> its ring slot (last read AHEAD barriers ago) and the loads
-    // of stage it+AHEAD+NSET refill the register set
-    auto step = [&](int it, float (&xa)[NSA][8], float (&xb)[NSB][8]) {
-      if (it + AHEAD < nk) {
-        put(xa, xb);
-        if (it + AHEAD + NSET < nk) issue(xa, xb);
-      }
-      __syncthreads();
-    };
-    for (int it = 0; it < nk; it += NSET) {
-#pragma unroll
-      for (int u = 0; u < NSET; ++u)
-        if (it + u < nk) step(it + u, ra[(AHEAD + u) % NSET], rb[(AHEAD + u) % NSET]);
-    }
+    split_pump<RING>(nk, ra, rb, issue, put);
     if (!A_KC && do_rowsum && m0 + ptid < d.M) atomicAdd(d.a_rowsum + m0 + ptid, d.alpha * rsum);
     if (!TRANS && g.epi_vec) {   // the two barriers of the consumers' LDS-transposed epilogue
       __syncthreads();
@@ -367,60 +408,19 @@ __global__ __launch_bounds__(SplitCfg<BM>::NTHR, SplitCfg<BM>::BLOCKS_PER_CU) vo
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  // per-lane fragment base: row (l31); lane-half h takes k 8h..8h+7 of the 16-k MFMA step
   const int a_frag = ((wm * TM) * 32 + l31) * XROWB + h * 16;
   const int b_frag = A_BYTES + ((wn * TN) * 32 + l31) * XROWB + h * 16;
-  uint4 fa[2][TM][3], fb[2][TN][3];
-  int rbuf = 0;   // ring slot of the next fragment read
-  auto read_frags = [&](uint4 (&xa)[TM][3], uint4 (&xb)[TN][3]) {
-    const char* st = lds + rbuf * STAGE;
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-        xa[i][s] = *reinterpret_cast<const uint4*>(st + a_frag + i * 32 * XROWB + s * 2 * XBK);
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-        xb[j][s] = *reinterpret_cast<const uint4*>(st + b_frag + j * 32 * XROWB + s * 2 * XBK);
-    }
-    rbuf = (rbuf == RING - 1) ? 0 : rbuf + 1;
-  };
-  // term pairs (i, j) with i + j <= 2, smallest first; the four accumulators are interleaved so that dependent
-  // MFMAs are four issues apart
-  auto mfmas = [&](uint4 (&xa)[TM][3], uint4 (&xb)[TN][3]) {
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-      constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
-      constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = TRANS ? fd::mfma_32x32x16_bf16(xb[j][PB[p]], xa[i][PA[p]], acc[i][j])
-                            : fd::mfma_32x32x16_bf16(xa[i][PA[p]], xb[j][PB[p]], acc[i][j]);
-    }
-  };
-
+  int rbuf = 0;
   __syncthreads();   // the first stages are in the ring
   if (RING == 3) {
-    // stage it is multiplied out of registers while the fragments of stage it+1 (complete in the ring since the
-    // last barrier) are fetched; the barrier itself carries no LDS wait on this side
-    auto step = [&](int it, uint4 (&ca)[TM][3], uint4 (&cb)[TN][3], uint4 (&na)[TM][3], uint4 (&nb)[TN][3]) {
-      if (it + 1 < nk) read_frags(na, nb);
-      mfmas(ca, cb);
-      fd::block_barrier_nofence();
-    };
-    read_frags(fa[0], fb[0]);
-    for (int it = 0; it < nk; it += 2) {
-      step(it, fa[0], fb[0], fa[1], fb[1]);
-      if (it + 1 < nk) step(it + 1, fa[1], fb[1], fa[0], fb[0]);
-    }
+    split_multiply3<BM, TRANS>(acc, nk, lds, rbuf, a_frag, b_frag);
   } else {
     // two-stage ring: stage it+1 is only complete at the barrier that ends stage it, so its fragments are fetched
     // after the barrier; the co-resident second block covers that latency
+    uint4 fa[TM][3], fb[TN][3];
     for (int it = 0; it < nk; ++it) {
-      read_frags(fa[0], fb[0]);
-      mfmas(fa[0], fb[0]);
+      split_read_frags<BM>(lds, rbuf, a_frag, b_frag, fa, fb);
+      fd_mma6<TRANS, TM, TN>(acc, fa, fb);
       fd::block_barrier_nofence();
     }
   }
@@ -449,10 +449,10 @@ template <bool B_KC>
 __global__ __launch_bounds__(SplitCfg<XBM>::NTHR, 1) void gemm_bx3p_kernel(GemmArgs g) {
   using Cfg = SplitCfg<XBM>;
   constexpr int BM = XBM, BN = XBN, TM = 2, TN = 2;
-  constexpr int NCONS = Cfg::NCONS, NPROD = Cfg::NPROD, STAGE = Cfg::STAGE, RING = 3;
+  constexpr int NCONS = Cfg::NCONS, NPROD = Cfg::NPROD, RING = 3;
   constexpr int A_BYTES = BM * XROWB;
   static_assert(Cfg::RING == 3, "ring");
-  __shared__ __attribute__((aligned(16))) char lds[RING * STAGE];
+  __shared__ __attribute__((aligned(16))) char lds[RING * Cfg::STAGE];
 
   const FdGemmDesc& d = g.d;
   const int tid = (int)threadIdx.x;
@@ -462,7 +462,7 @@ __global__ __launch_bounds__(SplitCfg<XBM>::NTHR, 1) void gemm_bx3p_kernel(GemmA
   const int z = (int)blockIdx.y;
   const int zo = z / d.bdiv, zi = z % d.bdiv;
   const int nk = (d.K + XBK - 1) / XBK;
-  const int total = ntiles * nk;
+  const int total = ntiles * nk;   // the producers' stream: every stage of every tile of this block
 
   if (tid >= NCONS) {
     const int ptid = tid - NCONS;
@@ -472,8 +472,7 @@ __global__ __launch_bounds__(SplitCfg<XBM>::NTHR, 1) void gemm_bx3p_kernel(GemmA
     SplitStager<BM, true, NPROD> sa;
     SplitStager<BN, B_KC, NPROD> sb;
     constexpr int NSA = SplitStager<BM, true, NPROD>::NS, NSB = SplitStager<BN, B_KC, NPROD>::NS;
-    constexpr int NSET = 2;
-    float ra[NSET][NSA][8], rb[NSET][NSB][8];
+    float ra[XNSET][NSA][8], rb[XNSET][NSB][8];
     int lt = first, lk = 0;   // tile and k stage of the next global load
     {
       const int lid = fd_xcd_swizzle(lt, nblk);
@@ -494,35 +493,8 @@ __global__ __launch_bounds__(SplitCfg<XBM>::NTHR, 1) void gemm_bx3p_kernel(GemmA
       }
     };
     int wbuf = 0;
-    auto put = [&](float (&xa)[NSA][8], float (&xb)[NSB][8]) {
-      char* dst = lds + wbuf * STAGE;
-      sa.store(xa, dst);
-      sb.store(xb, dst + A_BYTES);
-      wbuf = (wbuf == RING - 1) ? 0 : wbuf + 1;
-    };
-    constexpr int AHEAD = RING - 1;
-#pragma unroll
-    for (int u = 0; u < NSET; ++u)
-      if (u < total) issue(ra[u], rb[u]);
-#pragma unroll
-    for (int u = 0; u < AHEAD; ++u)
-      if (u < total) {
-        put(ra[u], rb[u]);
-        if (u + NSET < total) issue(ra[u], rb[u]);
-      }
-    __syncthreads();
-    auto step = [&](int it, float (&xa)[NSA][8], float (&xb)[NSB][8]) {
-      if (it + AHEAD < total) {
-        put(xa, xb);
-        if (it + AHEAD + NSET < total) issue(xa, xb);
-      }
-      __syncthreads();
-    };
-    for (int it = 0; it < total; it += NSET) {
-#pragma unroll
-      for (int u = 0; u < NSET; ++u)
-        if (it + u < total) step(it + u, ra[(AHEAD + u) % NSET], rb[(AHEAD + u) % NSET]);
-    }
+    auto put = [&](float (&xa)[NSA][8], float (&xb)[NSB][8]) { split_put<BM>(sa, sb, lds, wbuf, xa, xb); };
+    split_pump<RING>(total, ra, rb, issue, put);
     return;
   }
 
@@ -542,41 +514,7 @@ __global__ __launch_bounds__(SplitCfg<XBM>::NTHR, 1) void gemm_bx3p_kernel(GemmA
       for (int j = 0; j < TN; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    uint4 fa[2][TM][3], fb[2][TN][3];
-    auto read_frags = [&](uint4 (&xa)[TM][3], uint4 (&xb)[TN][3]) {
-      const char* st = lds + rbuf * STAGE;
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-          xa[i][s] = *reinterpret_cast<const uint4*>(st + a_frag + i * 32 * XROWB + s * 2 * XBK);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          xb[j][s] = *reinterpret_cast<const uint4*>(st + b_frag + j * 32 * XROWB + s * 2 * XBK);
-      }
-      rbuf = (rbuf == RING - 1) ? 0 : rbuf + 1;
-    };
-    auto mfmas = [&](uint4 (&xa)[TM][3], uint4 (&xb)[TN][3]) {
-#pragma unroll
-      for (int p = 0; p < 6; ++p) {
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
-        constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = fd::mfma_32x32x16_bf16(xb[j][PB[p]], xa[i][PA[p]], acc[i][j]);
-      }
-    };
-    auto step = [&](int it, uint4 (&ca)[TM][3], uint4 (&cb)[TN][3], uint4 (&na)[TM][3], uint4 (&nb)[TN][3]) {
-      if (it + 1 < nk) read_frags(na, nb);
-      mfmas(ca, cb);
-      fd::block_barrier_nofence();
-    };
-    read_frags(fa[0], fb[0]);
-    for (int it = 0; it < nk; it += 2) {
-      step(it, fa[0], fb[0], fa[1], fb[1]);
-      if (it + 1 < nk) step(it + 1, fa[1], fb[1], fa[0], fb[0]);
-    }
+    split_multiply3<BM, true>(acc, nk, lds, rbuf, a_frag, b_frag);
     const int lid = fd_xcd_swizzle(first + ti * G, nblk);
     const int mb = (lid / g.nblk_n) * BM + wm * TM * 32, nb = (lid % g.nblk_n) * BN + wn * TN * 32;
     store_tile_t<TM, TN>(d, C, acc, mb, nb, h, l31, g.epi_vec != 0);

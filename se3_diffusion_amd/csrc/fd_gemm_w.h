@@ -2,7 +2,7 @@
 // M = B*N residue rows of a few thousand against the per-residue nn.Linear weights (model/ipa_pytorch.py:334-374 IPA
 // projections, :465-469 linear_out, :169-191 node transition, :584-595 sequence transformer, :625-649 block body) -- the
 // forward y = x W^T and the activation gradient dx = dy W.  Included by fd_gemm.hip inside its anonymous namespace (uses
-// GemmArgs, store_tile, store_tile_t, s64_split4).
+// GemmArgs, store_tile, store_tile_t; the split of the activation fragment and the product order are fd_split.h's).
 //
 // What is different from tiles 4 / 10 (which split BOTH operands in registers on the way to LDS):
 //   * the weight operand arrives already split: fd_split_planes writes the three exact bf16 planes of the whole flat parameter
@@ -181,8 +181,8 @@ __global__ __launch_bounds__(256, (WCfg<BM, BN, B_KC>::BLOCKS_PER_CU)) void gemm
         a0 = make_uint2(__float_as_uint(xa[i][0].x), __float_as_uint(xa[i][0].y)); a1 = a0; a2 = a0;
         b0 = make_uint2(__float_as_uint(xa[i][1].x), __float_as_uint(xa[i][1].y)); b1 = b0; b2 = b0;
       } else {
-        s64_split4(xa[i][0], a0, a1, a2);
-        s64_split4(xa[i][1], b0, b1, b2);
+        fd_split4(xa[i][0], a0, a1, a2);
+        fd_split4(xa[i][1], b0, b1, b2);
       }
       fa[i][0] = make_uint4(a0.x, a0.y, b0.x, b0.y);
       fa[i][1] = make_uint4(a1.x, a1.y, b1.x, b1.y);
@@ -192,18 +192,7 @@ __global__ __launch_bounds__(256, (WCfg<BM, BN, B_KC>::BLOCKS_PER_CU)) void gemm
       acc[0][0][0] += __uint_as_float(fa[0][0].x ^ fb[0][0].x ^ fa[TM - 1][2].w ^ fb[TN - 1][2].w);
       return;
     }
-    // the six products with i + j <= 2, small terms first; the TM x TN accumulators interleaved
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-      constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
-      constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = TRANS ? fd::mfma_32x32x16_bf16(fb[j][PB[p]], fa[i][PA[p]], acc[i][j])
-                            : fd::mfma_32x32x16_bf16(fa[i][PA[p]], fb[j][PB[p]], acc[i][j]);
-    }
+    fd_mma6<TRANS, TM, TN>(acc, fa, fb);   // the six products with i + j <= 2, small terms first
   };
 
   // stage s lives in ring slot s % RING and is copied RING - 1 stages before it is multiplied.  The vector-memory counter retires in
@@ -244,8 +233,8 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (long)gridDim.x * blockDim.x) {
     const float4 a = *reinterpret_cast<const float4*>(x + 8 * i), b = *reinterpret_cast<const float4*>(x + 8 * i + 4);
     uint2 a0, a1, a2, b0, b1, b2;
-    s64_split4(a, a0, a1, a2);
-    s64_split4(b, b0, b1, b2);
+    fd_split4(a, a0, a1, a2);
+    fd_split4(b, b0, b1, b2);
     *reinterpret_cast<uint4*>(planes + 8 * i) = make_uint4(a0.x, a0.y, b0.x, b0.y);
     *reinterpret_cast<uint4*>(planes + n + 8 * i) = make_uint4(a1.x, a1.y, b1.x, b1.y);
     *reinterpret_cast<uint4*>(planes + 2 * n + 8 * i) = make_uint4(a2.x, a2.y, b2.x, b2.y);

@@ -77,7 +77,7 @@ __device__ __forceinline__ void gd_unit(const GdUnit& u, char* lds, const int db
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       uint2 s0, s1, s2;
-      dw_split4(r[i], s0, s1, s2);
+      fd_split4(r[i], s0, s1, s2);
       const int o = ((i & 2) ? wB : wA) + (i & 1) * 8 * 64;
       *reinterpret_cast<uint2*>(dst + o) = s0;
       *reinterpret_cast<uint2*>(dst + GD_PLANE + o) = s1;
@@ -97,25 +97,7 @@ __device__ __forceinline__ void gd_unit(const GdUnit& u, char* lds, const int db
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  auto mma = [&](const char* st) __attribute__((always_inline)) {
-    uint4 fb[2][3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) fb[j][s] = dw_read8(st + b_rd + j * DW_PSTRIDE + s * GD_PLANE);
-#pragma unroll
-    for (int sa = 2; sa >= 0; --sa) {   // the small terms first
-      uint4 fa[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) fa[i] = dw_read8(st + a_rd + i * DW_PSTRIDE + sa * GD_PLANE);
-#pragma unroll
-      for (int sb = 2 - sa; sb >= 0; --sb)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[i][j] = fd::mfma_32x32x16_bf16(fa[i], fb[j][sb], acc[i][j]);
-    }
-  };
+  auto mma = [&](const char* st) __attribute__((always_inline)) { dw_mma6<false, 2, GD_PLANE>(acc, st, a_rd, b_rd); };
 
   // full stages through running pointers (no clamp / select of the row index)
   const float* pa = A + ((long)(GD_NSET + 1) * DW_KS + kk) * u.lda + ca;

@@ -8,7 +8,7 @@
 // tensors as the fused forward / backward kernels left them, so the reduction index p is the STRIDED one of both --
 // the shape fd_gemm's split kernel stages with 8 dword loads per 8-k slot.  Here:
 //   * a thread loads float4s along the feature axis (whole 128-byte lines per 8 lanes), splits them into the three
-//     bf16 planes (fp32-accurate split-bf16 arithmetic, as fd_gemm tile 4) and writes each plane as ds_write_b64
+//     bf16 planes (fp32-accurate split-bf16 arithmetic, as fd_gemm tile 4: fd_split.h) and writes each plane as ds_write_b64
 //     into a [panel of 32 columns][k][32] image;
 //   * the MFMA operands are read back with ds_read_b64_tr_b16 (the LDS transpose read of gfx950): two reads give a
 //     lane its column's 8 consecutive k of a v_mfma_f32_32x32x16_bf16 operand -- no transposition in registers;
@@ -97,7 +97,7 @@ __device__ __forceinline__ void dw_block(const FdPairDwItem& it, long row0, long
     for (int i = 0; i < 4; ++i) {
       if (i >= NA && i != 3) continue;
       uint2 s0, s1, s2;
-      dw_split4(r[i], s0, s1, s2);
+      fd_split4(r[i], s0, s1, s2);
       *reinterpret_cast<uint2*>(dst + wofs[i]) = s0;
       *reinterpret_cast<uint2*>(dst + DW_PLANE + wofs[i]) = s1;
       *reinterpret_cast<uint2*>(dst + 2 * DW_PLANE + wofs[i]) = s2;
@@ -116,27 +116,7 @@ __device__ __forceinline__ void dw_block(const FdPairDwItem& it, long row0, long
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  auto mma = [&](const char* st) __attribute__((always_inline)) {
-    uint4 fb[2][3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) fb[j][s] = dw_read8(st + b_rd + j * DW_PSTRIDE + s * DW_PLANE);
-#pragma unroll
-    for (int sa = 2; sa >= 0; --sa) {   // the small terms first
-      uint4 fa[NA];
-#pragma unroll
-      for (int i = 0; i < NA; ++i) fa[i] = dw_read8(st + a_rd + i * DW_PSTRIDE + sa * DW_PLANE);
-#pragma unroll
-      for (int sb = 2 - sa; sb >= 0; --sb)
-#pragma unroll
-        for (int i = 0; i < NA; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = TRANS ? fd::mfma_32x32x16_bf16(fb[j][sb], fa[i], acc[i][j])
-                              : fd::mfma_32x32x16_bf16(fa[i], fb[j][sb], acc[i][j]);
-    }
-  };
+  auto mma = [&](const char* st) __attribute__((always_inline)) { dw_mma6<TRANS, NA, DW_PLANE>(acc, st, a_rd, b_rd); };
 
   // Stages that lie entirely inside the row range are loaded through running pointers without the clamp / select of
   // load() (it costs ~35 of the ~135 VALU instructions a wave spends per stage, six of them quarter-rate 32-bit

@@ -1,7 +1,9 @@
 """Exact-integer probes of the six split-bf16 products, at every kernel that forms them.
 
 An fp32 operand is split into three bf16 planes x = x0 + x1 + x2, and the six products a_i b_j with i + j <= 2 are
-accumulated in fp32 (fd_gemm tiles 4 / 6 / 10 / 12 / 13 / 14, fd_pair_dw, fd_group_dw, the register-chained edge transition).
+accumulated in fp32 (fd_gemm tiles 4 / 6 / 10 / 12 / 13 / 14, fd_pair_dw, fd_group_dw, the register-chained edge transition;
+the split and the product order are defined once, in csrc/fd_split.h, the plane-major order of the two *_dw kernels in
+csrc/fd_pair_dw_common.h).
 The parity tests of these kernels draw N(0, 1) operands and bound the error by a fraction of the tensor's maximum; a missing
 second-order product (2^-17 relative to one term) is about as large as that bound, so they cannot tell whether all six products
 are there.  Here the operands are integer-valued fp32 of three classes

@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void node_chain_pack_kernel(NcMat A, int W, in
     x[e] = A.p[(long)n * A.rs + (long)k * A.cs];
   }
   uint4 s0, s1, s2;
-  em_split8(x, s0, s1, s2);
+  fd_split8(x, s0, s1, s2);
   char* dst = img + (long)u * EM_UNIT + (i * 3) * EM_PIECE + lane * 16;
   *reinterpret_cast<uint4*>(dst) = s0;
   *reinterpret_cast<uint4*>(dst + EM_PIECE) = s1;
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(64 * EM_WAVES, 1) void node_chain_kernel(FdNodeChai
             const int u = EM_UPS * sg + (hh >> 1), ks = u / NG, ng = u % NG, a = 4 * ng + 2 * (hh & 1);
             if (hh + 1 < 2 * EM_UPS) em16_read_half(H[(hh + 1) & 1], st + (hh + 1) * (EM_UNIT / 2));
             fd::sched_pin();
-            if (ng == 0 && (hh & 1) == 0) em_split8(xr[ks], b[0], b[1], b[2]);
+            if (ng == 0 && (hh & 1) == 0) fd_split8(xr[ks], b[0], b[1], b[2]);
             em16_mma_half(P[a], P[a + 1], H[hh & 1], b);
             if (hh == 1) stage_prefetch();
           }

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(DW_THREADS, 1) void pair_dw_diag_kernel(FdPairDwDia
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       uint2 t0, t1, t2;
-      dw_split4(r[i], t0, t1, t2);
+      fd_split4(r[i], t0, t1, t2);
       char* o = dst + (i < 3 ? 4 * i : 12 + 4 * (i - 3)) * DW_PSTRIDE + wsub;
       *reinterpret_cast<uint2*>(o) = t0;
       *reinterpret_cast<uint2*>(o + DD_PLANE) = t1;

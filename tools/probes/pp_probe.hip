@@ -4,13 +4,13 @@
 // Skeleton of csrc/fd_edge_mlp.hip's dataflow without its epilogues: a wave owns 16 rows, 96 accumulator registers, per weight
 // unit (12 KB = 4 n-blocks x one 32-k step x 3 bf16 planes): 12 ds_read_b128 + 24 v_mfma_f32_16x16x32_bf16; every 6th unit a
 // 3-way bf16 split of 8 values (44 VALU); the weight image streams through an LDS ring by LDS-DMA.  One 8-wave block per CU.
-//   hipcc --offload-arch=gfx950 -O3 pp_probe.hip -o pp_probe && ./pp_probe
+//   hipcc --offload-arch=gfx950 -O3 -I ../../se3_diffusion_amd/csrc/gfx950 -I ../../se3_diffusion_amd/csrc pp_probe.hip -o pp_probe && ./pp_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include <fd_intrin.h>     // csrc/gfx950: pack_bf16 (a conversion the compiler sees, so that it keeps the wait states in front of the MFMAs)
+#include "fd_split.h"      // csrc: the split and the six-product order of the shipped kernels
 
 constexpr int PIECE = 1024, UNIT = 12 * PIECE, NUNITS = 128;
 #ifndef RING
@@ -20,31 +20,7 @@ constexpr int PIECE = 1024, UNIT = 12 * PIECE, NUNITS = 128;
 #define AHEAD 4
 #endif
 
-__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  // (as csrc/gfx950/fd_intrin.h: a conversion the compiler sees, so that it keeps the wait states in front of the MFMAs)
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ void split8(const float (&x)[8], uint4& s0, uint4& s1, uint4& s2) {
-  unsigned t0[4], t1[4], t2[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float u = x[2 * j], v = x[2 * j + 1];
-    const unsigned hh = pack_bf16(u, v);
-    const float ru = u - __builtin_bit_cast(float, hh << 16), rv = v - __builtin_bit_cast(float, hh & 0xffff0000u);
-    const unsigned mm = pack_bf16(ru, rv);
-    const float qu = ru - __builtin_bit_cast(float, mm << 16), qv = rv - __builtin_bit_cast(float, mm & 0xffff0000u);
-    t0[j] = hh; t1[j] = mm; t2[j] = pack_bf16(qu, qv);
-  }
-  s0 = make_uint4(t0[0], t0[1], t0[2], t0[3]);
-  s1 = make_uint4(t1[0], t1[1], t1[2], t1[3]);
-  s2 = make_uint4(t2[0], t2[1], t2[2], t2[3]);
-}
+__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c) { return fd::mfma_16x16x32_bf16(a, b, c); }
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
   return (unsigned)(unsigned long long)(const __attribute__((address_space(3))) char*)p;
 }
@@ -76,8 +52,8 @@ __global__ __launch_bounds__(512, 2) void k(const char* __restrict__ img, float*
 #pragma unroll
   for (int e = 0; e < 8; ++e) x[e] = 0.01f * (lane + e) + 0.5f;
   uint4 b[3], b2[3], H[12];
-  split8(x, b[0], b[1], b[2]);
-  split8(x, b2[0], b2[1], b2[2]);
+  fd_split8(x, b[0], b[1], b[2]);
+  fd_split8(x, b2[0], b2[1], b2[2]);
   const int total = tiles * NUNITS;
   // pieces of unit u issued by this wave: piece p by wave p % 8 (waves 0..3: two pieces, waves 4..7: one)
   int iu = 0, islot = 0, isrc = 0;        // next unit to copy, its ring slot, its index in the image
@@ -100,11 +76,10 @@ __global__ __launch_bounds__(512, 2) void k(const char* __restrict__ img, float*
     for (int i = 0; i < 12; ++i) H[i] = *reinterpret_cast<const uint4*>(s + i * PIECE);
   };
   auto mma_unit = [&](int a0) __attribute__((always_inline)) {
-    constexpr int PW[6] = {2, 1, 0, 1, 0, 0}, PX[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
     for (int p = 0; p < 6; ++p)
 #pragma unroll
-      for (int nb = 0; nb < 4; ++nb) acc[a0 + nb] = mfma(H[3 * nb + PW[p]], b[PX[p]], acc[a0 + nb]);
+      for (int nb = 0; nb < 4; ++nb) acc[a0 + nb] = mfma(H[3 * nb + FD_PA[p]], b[FD_PB[p]], acc[a0 + nb]);
   };
   auto read_half = [&]() __attribute__((always_inline)) {
     const char* s = ring + rslot * UNIT + ((wave & 1) * 6) * PIECE + lane * 16;
@@ -113,13 +88,12 @@ __global__ __launch_bounds__(512, 2) void k(const char* __restrict__ img, float*
     for (int i = 0; i < 6; ++i) H[i] = *reinterpret_cast<const uint4*>(s + i * PIECE);
   };
   auto mma_half2 = [&](int a0) __attribute__((always_inline)) {
-    constexpr int PW[6] = {2, 1, 0, 1, 0, 0}, PX[6] = {0, 1, 2, 0, 1, 0};
 #pragma unroll
     for (int p = 0; p < 6; ++p)
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
-        acc[a0 + 2 * nb] = mfma(H[3 * nb + PW[p]], b[PX[p]], acc[a0 + 2 * nb]);
-        acc[a0 + 2 * nb + 1] = mfma(H[3 * nb + PW[p]], b2[PX[p]], acc[a0 + 2 * nb + 1]);
+        acc[a0 + 2 * nb] = mfma(H[3 * nb + FD_PA[p]], b[FD_PB[p]], acc[a0 + 2 * nb]);
+        acc[a0 + 2 * nb + 1] = mfma(H[3 * nb + FD_PA[p]], b2[FD_PB[p]], acc[a0 + 2 * nb + 1]);
       }
   };
   if (MODE == 0) {
@@ -145,11 +119,11 @@ __global__ __launch_bounds__(512, 2) void k(const char* __restrict__ img, float*
         if (g == 0) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) x[e] = acc[e >> 2][e & 3] * 0.5f + x[e] * 0.25f;
-          split8(x, b[0], b[1], b[2]);
+          fd_split8(x, b[0], b[1], b[2]);
           if (MODE == 4) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[e] = acc[2 + (e >> 2)][e & 3] * 0.5f + x[e] * 0.25f;
-            split8(x, b2[0], b2[1], b2[2]);
+            fd_split8(x, b2[0], b2[1], b2[2]);
           }
         }
         issue();

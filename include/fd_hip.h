@@ -936,6 +936,85 @@ int fd_dssp_hbonds(const float* atoms, long atom_stride, const float* res_mask, 
 int fd_dssp_assign(const float* atoms, long atom_stride, int natoms, const float* res_mask, const int* acc_idx, const double* acc_e,
                    int B, int N, signed char* ss, double* out, void* stream);
 
+/* ---- bond, angle and clash violation losses (se3_diffusion_amd/csrc/fd_violations.hip) ----
+ * The INTER_VIOLATION_METRICS of the reference's metrics.csv (analysis/metrics.py:13-42: bonds_c_n_loss_mean,
+ * angles_ca_c_n_loss_mean, clashes_mean_loss) and what comes with them, which the reference computes per sample on the host:
+ * amber_minimize.find_violations (openfold/np/relax/amber_minimize.py:354-390) builds atom14 arrays of a full-atom Protein and
+ * calls openfold/utils/loss.py::find_structural_violations (:1105-1215) with violation_tolerance_factor 12 and
+ * clash_overlap_tolerance 1.5 (amber_minimize.py:377-382), then compute_violation_metrics (:1272-1312).  Here: the same arithmetic
+ * for an ALL-ALANINE chain -- the atoms a backbone sampler has: N, CA, C, CB, O -- so there is no proline branch and no disulfide
+ * branch.  Operands as fd_backbone_metrics (residue r of backbone b at atoms + (b N + r) atom_stride floats, N, CA, C, CB, O in
+ * slots 0..4, read in place; present iff res_mask[b,r] != 0; B == 0 or N == 0 returns FD_OK without a launch and writes nothing).
+ * res_index (optional) [B,N] int32: the residue numbers; NULL means the position in the padded chain.  N <= FD_VIOLATIONS_MAX_N =
+ * 2048: every block keeps the five atoms of a whole chain in LDS (fifteen fp32 arrays, 120 KB, and 20 KB of radii and index maps).
+ *
+ * All decisions are made in fp64 from the fp32 coordinates.
+ *   residues      the present residues, compacted in index order: 0 .. n-1, residue k with number idx(k) = res_index of it.
+ *   connections   (between_residue_bond_loss, loss.py:712-868) between k and k+1, for k = 0 .. n-2, with eps = 1e-6 INSIDE every
+ *                 square root as the reference has it: l_cn = sqrt(eps + |C(k) - N(k+1)|^2), l_cac = sqrt(eps + |CA(k) - C(k)|^2),
+ *                 l_nca = sqrt(eps + |N(k+1) - CA(k+1)|^2); cos1 = (CA(k) - C(k)) / l_cac . (N(k+1) - C(k)) / l_cn;
+ *                 cos2 = -(N(k+1) - C(k)) / l_cn . (CA(k+1) - N(k+1)) / l_nca.
+ *                   e0 = sqrt(eps + (l_cn - 1.329)^2)    tolerance t0 = 12 * 0.014
+ *                   e1 = sqrt(eps + (cos1 + 0.4473)^2)   tolerance t0 AGAIN: the reference takes the C-N length's standard
+ *                        deviation here (loss.py:807), not the cosine's own 0.0311.  A quirk of the reference, kept.
+ *                   e2 = sqrt(eps + (cos2 + 0.5203)^2)   tolerance t2 = 12 * 0.0353
+ *                 loss_x = relu(e_x - t_x).  bonded(k) = idx(k+1) - idx(k) == 1.  The three means are
+ *                 sum over bonded k of loss_x / (number of bonded k + eps).  violated(k) = bonded(k) and some e_x > t_x.
+ *                 connections_per_residue_loss_sum(k) = 0.5 ((loss_0 + loss_1 + loss_2)(k) + (the same)(k-1)), a missing neighbour
+ *                 giving 0 -- over ALL consecutive present residues, bonded or not: the reference does not mask this sum
+ *                 (loss.py:841-847).  connections_per_residue_violation_mask(k) = violated(k) or violated(k-1).
+ *   clashes       (between_residue_clash_loss, loss.py:871-1015) all pairs of an atom a of residue i and an atom c of residue j
+ *                 with idx(i) < idx(j), except the pair (C of i, N of j) where idx(j) == idx(i) + 1 (:935-959).  Radii: N 1.55;
+ *                 CA, C, CB 1.7; O 1.52.  dist = sqrt(1e-10 + d^2), bound = r_a + r_c - 1.5, loss = relu(bound - dist), a clash
+ *                 iff dist < bound.  clashes_mean_loss = sum of loss / (1e-6 + number of counted pairs).
+ *                 clashes_per_atom_loss_sum(i, a): the losses of all counted pairs the atom is in, as first or as second member
+ *                 (both triangles, :994-996); clashes_per_atom_clash_mask(i, a): it is in a clash.
+ *   fractions     (compute_violation_metrics, loss.py:1272-1312, with tensor_utils.masked_mean's eps = 1e-4 and seq_mask = 1 on
+ *                 the present residues) extreme CA-CA: bonded k with sqrt(1e-6 + |CA(k) - CA(k+1)|^2) - 3.80209737096 > 1.5, over
+ *                 (1e-4 + number of bonded k); the others: residues with the mask set / (1e-4 + n).
+ *
+ * out[b][0..FD_VIOLATION_SLOTS) =
+ *   0 num_res                            n
+ *   1 bonds_c_n_loss_mean                2 angles_ca_c_n_loss_mean         3 angles_c_n_ca_loss_mean
+ *   4 clashes_mean_loss
+ *   5 violations_extreme_ca_ca_distance
+ *   6 violations_between_residue_bond    residues with connections_per_residue_violation_mask
+ *   7 violations_between_residue_clash   residues with an atom in a clash
+ *   8 violations_per_residue             residues with either.  NOT the reference's value when a residue is distorted within
+ *                                        itself: see the second difference below.
+ *   9 num_residue_violations             the count behind slot 8 (the reference: the sum of total_per_residue_violations_mask)
+ *   10 num_bonds                         bonded k
+ *   11 num_atom_pairs                    counted atom pairs
+ *   12 num_clashing_pairs                counted atom pairs that clash
+ *   13..15                               0
+ * n == 0 (and n == 1) give counts 0 and the means the formulas give with their eps: 0.
+ * Optional arrays, by ORIGINAL residue index, every element written, zeros at absent residues; NULL skips one:
+ *   res_loss [B,N] fp64     connections_per_residue_loss_sum
+ *   atom_loss [B,N,5] fp64  clashes_per_atom_loss_sum, atoms in the order N, CA, C, CB, O
+ *   flags [B,N] uint8       bit a (0..4): clashes_per_atom_clash_mask of atom a; bit 5: connections_per_residue_violation_mask
+ *
+ * Two deliberate differences from the reference:
+ *   absent residues   a residue with res_mask == 0 takes no part, and the bond across it is a gap.  The reference leaves such a
+ *                 residue at the origin with atom14_atom_exists = 1 -- atom14 existence follows the residue type, not the atom
+ *                 mask -- so that every masked residue clashes with every other masked one.  What agrees with the reference is the
+ *                 run on the compacted chain with residue_index carrying the original positions.
+ *   within-residue term   within_residue_violations (loss.py:1018-1102) is left out: the sampler builds N, CA, C, CB and O of a
+ *                 residue from ideal geometry, so the term is zero by construction for its output.  violations_per_residue and
+ *                 num_residue_violations are therefore the maximum of the connection mask and the clash mask only, and
+ *                 violations_within_residue is not reported.
+ *
+ * Two launches (a grid of ceil(N / FD_VIOLATIONS_TILE) B blocks, then one thread per backbone), no host synchronisation, no
+ * floating-point atomics, every sum in a fixed order that depends only on the compacted chain: results are bitwise reproducible and
+ * bitwise independent of B, of the backbone's place in the batch and of absent residues behind it.  ws: FD_VIOLATIONS_WS_DOUBLES(B, N)
+ * doubles, need not be initialised.  Refused before any launch: N above the limit, atom_stride < 15, a null atoms, res_mask, ws or
+ * out, a misaligned operand. */
+#define FD_VIOLATION_SLOTS 16
+#define FD_VIOLATIONS_MAX_N 2048
+#define FD_VIOLATIONS_TILE 64
+#define FD_VIOLATIONS_WS_DOUBLES(B, N) ((long)(B) * (((long)(N) + FD_VIOLATIONS_TILE - 1L) / FD_VIOLATIONS_TILE) * 16L)
+int fd_violations(const float* atoms, long atom_stride, const float* res_mask, const int* res_index, int B, int N, double* ws,
+                  double* out, double* res_loss, double* atom_loss, unsigned char* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,7 @@ _SIGS = {
     "fd_tm_align": "pliplipppp" + "iiii" + "pppp" + "s",
     "fd_dssp_hbonds": "plppiipps",
     "fd_dssp_assign": "plipppiipps",
+    "fd_violations": "plppiippppps",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

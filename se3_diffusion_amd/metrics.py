@@ -25,8 +25,18 @@ specification) and radius_of_gyration as mdtraj's compute_rg defines it (all ato
 and the host round trip of the reference.  NOT verified: no DSSP program and no mdtraj exists where this project is built, so
 agreement with the letters md.compute_dssp prints has never been checked; the tests check a float64 restatement and its
 plausibility against the HELIX / SHEET records of six deposited structures.  Two deliberate differences from the DSSP program:
-the H-bond energy is not rounded to three decimals, and the gaps of a bulge must be non-negative.  Still not here (DESIGN.md
-section 8): the OpenMM violation losses, solvent accessibility, and the sheet-label and bridge-partner columns of a DSSP record.
+the H-bond energy is not rounded to three decimals, and the gaps of a bulge must be non-negative.
+
+violations: the reference's INTER_VIOLATION_METRICS (analysis/metrics.py:13-17) -- bonds_c_n_loss_mean, angles_ca_c_n_loss_mean,
+clashes_mean_loss -- with angles_c_n_ca_loss_mean, the per-residue and per-atom arrays and compute_violation_metrics' fractions:
+openfold/utils/loss.py's between_residue_bond_loss, between_residue_clash_loss and compute_violation_metrics for an all-alanine
+chain, under amber_minimize.find_violations' tolerances (fd_violations; include/fd_hip.h is the specification), without the Protein
+object, the atom14 arrays and the [N,N,14,14] tensors of the reference.  Verified against the unmodified reference functions, run
+in float32 and in float64 on the compacted chain (tests/golden/violations.npz).  Two deliberate differences: an absent residue
+takes no part (the reference would leave it at the origin, existing), and the within-residue term is left out (zero by
+construction for a backbone built from ideal geometry), so violations_per_residue and num_residue_violations take the connection
+and clash masks only.  Still not here: that within-residue term and the OpenMM relaxation itself, solvent
+accessibility, and the sheet-label and bridge-partner columns of a DSSP record.
 
 Every value stays on the device as float64; only eval_rows copies to the host, once.
 """
@@ -50,6 +60,15 @@ SHAPE_SLOTS = ("num_res", "helix_percent", "strand_percent", "coil_percent", "no
                "num_hbonds", "overflow")
 SHAPE_COLUMNS = ("coil_percent", "helix_percent", "strand_percent", "non_coil_percent", "radius_of_gyration")    # the reference's names
 DSSP_MAX_N = 2048        # FD_DSSP_MAX_N: fd_dssp_hbonds keeps C, O and CA of a whole chain in LDS (80 KB of a CU's 160 KB)
+VIOLATION_SLOTS = ("num_res", "bonds_c_n_loss_mean", "angles_ca_c_n_loss_mean", "angles_c_n_ca_loss_mean", "clashes_mean_loss",
+                   "violations_extreme_ca_ca_distance", "violations_between_residue_bond", "violations_between_residue_clash",
+                   "violations_per_residue", "num_residue_violations", "num_bonds", "num_atom_pairs", "num_clashing_pairs")
+# the reference's INTER_VIOLATION_METRICS (analysis/metrics.py:13-17) first, then the fourth mean and compute_violation_metrics' fractions
+VIOLATION_COLUMNS = ("bonds_c_n_loss_mean", "angles_ca_c_n_loss_mean", "clashes_mean_loss", "angles_c_n_ca_loss_mean",
+                     "violations_extreme_ca_ca_distance", "violations_between_residue_bond", "violations_between_residue_clash",
+                     "violations_per_residue", "num_residue_violations")
+VIOLATIONS_MAX_N = 2048  # FD_VIOLATIONS_MAX_N: fd_violations keeps the five atoms of a whole chain in LDS (140 KB of a CU's 160 KB)
+VIOLATIONS_TILE = 64     # FD_VIOLATIONS_TILE
 SS_LETTERS = " HBEGITS"  # fd_dssp_assign's codes 0..7 (-1: the residue is absent)
 CA = 1                   # slot of CA in atom37 / the compact [.,5,3] order N, CA, C, CB, O
 
@@ -141,6 +160,59 @@ def secondary_structure(atoms, res_mask=None, no_donor=None, return_hbonds=False
     if return_hbonds:
         res["acc_idx"] = pick(acc_idx)
         res["acc_e"] = pick(acc_e)
+    return res
+
+
+def _violations_call(atoms, res_mask, res_index, per_residue):
+    """fd_violations on atoms [B,N,A,3]: out float64 [B,16], then res_loss [B,N], atom_loss [B,N,5], flags uint8 [B,N] (or None)"""
+    if atoms.dim() != 4 or atoms.shape[-1] != 3 or atoms.shape[-2] not in (5, 37):
+        raise ValueError(f"atoms of shape {tuple(atoms.shape)}: expected [B,N,37,3] or [B,N,5,3] (or the same without B)")
+    B, N, A = atoms.shape[:3]
+    if N > VIOLATIONS_MAX_N:
+        raise ValueError(f"violations: N = {N} residues, at most {VIOLATIONS_MAX_N} are supported")
+    atoms = _f32c(atoms)
+    dev = atoms.device
+    if res_mask is None:
+        res_mask = (atoms != 0).reshape(B, N, A * 3).any(-1)
+    res_mask = _f32c(res_mask.reshape(B, N))
+    if res_index is not None:
+        res_index = res_index.reshape(B, N).to(torch.int32).contiguous()
+    # (zeros, not empty: the entry point launches nothing on an empty chain, and zeros are what the formulas give there)
+    out = torch.zeros((B, 16), dtype=torch.float64, device=dev)
+    res_loss = atom_loss = flags = None
+    if per_residue:
+        res_loss = torch.zeros((B, N), dtype=torch.float64, device=dev)
+        atom_loss = torch.zeros((B, N, 5), dtype=torch.float64, device=dev)
+        flags = torch.zeros((B, N), dtype=torch.uint8, device=dev)
+    ws = torch.empty((max(1, B * (-(-N // VIOLATIONS_TILE)) * 16),), dtype=torch.float64, device=dev)     # FD_VIOLATIONS_WS_DOUBLES
+    hip.get_lib().call("fd_violations", atoms, A * 3, res_mask, res_index, B, N, ws, out, res_loss, atom_loss, flags)
+    return out, res_loss, atom_loss, flags
+
+
+def violations(atoms, res_mask=None, res_index=None, per_residue=False):
+    """The reference's between-residue violation losses (openfold/utils/loss.py: between_residue_bond_loss, between_residue_clash_loss,
+    compute_violation_metrics, with amber_minimize.find_violations' tolerances) of atoms [B,N,37,3] or [B,N,5,3] (atom order N, CA, C,
+    CB, O; or the same without B), read as an all-alanine chain: dict name -> float64 device tensor [B] (0-d without B) under
+    VIOLATION_SLOTS, the slot table of include/fd_hip.h, which also names the two deliberate differences (absent residues take no
+    part; no within-residue term).  res_mask as backbone_metrics; res_index [B,N]: residue numbers (None: the position in the padded
+    chain) -- a step other than 1 between consecutive present residues is a gap.  per_residue=True adds
+    connections_per_residue_loss_sum (float64 [B,N]), connections_per_residue_violation_mask (bool [B,N]),
+    clashes_per_atom_loss_sum (float64 [B,N,5]) and clashes_per_atom_clash_mask (bool [B,N,5]), zero at absent residues.
+    N <= 2048, or ValueError before anything is launched.  One call (two launches), no host synchronisation."""
+    batched = atoms.dim() == 4
+    if not batched:
+        atoms = atoms[None]
+        res_mask = None if res_mask is None else res_mask[None]
+        res_index = None if res_index is None else res_index[None]
+    out, res_loss, atom_loss, flags = _violations_call(atoms, res_mask, res_index, per_residue)
+    pick = (lambda x: x) if batched else (lambda x: x[0])
+    res = {name: pick(out[:, k]) for k, name in enumerate(VIOLATION_SLOTS)}
+    if per_residue:
+        bit = torch.arange(5, device=flags.device, dtype=torch.uint8)
+        res["connections_per_residue_loss_sum"] = pick(res_loss)
+        res["connections_per_residue_violation_mask"] = pick((flags & 32) != 0)
+        res["clashes_per_atom_loss_sum"] = pick(atom_loss)
+        res["clashes_per_atom_clash_mask"] = pick(((flags[..., None] >> bit) & 1) != 0)
     return res
 
 
@@ -436,7 +508,7 @@ def tm_align_matrix(pos_a, mask_a=None, pos_b=None, mask_b=None, search_step=40,
     return {name: out[:, TM_ALIGN_SLOTS.index(name)].reshape(Ma, Mb) for name in ("tm_norm_a", "tm_norm_b")}
 
 
-def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape=False):
+def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape=False, violations=False):
     """One dict of Python floats per backbone with the reference's column names (Experiment.eval_fn,
     experiments/train_se3_diffusion.py:475-508, and CA_VIOLATION_METRICS): ca_ca_bond_dev, ca_ca_valid_percent,
     ca_steric_clash_percent, num_ca_steric_clashes, num_res, fixed_residues, diffused_percentage -- and this module's own
@@ -446,7 +518,9 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape
     with tm="align" it adds tm_align_to_gt instead: tm_align's tm_norm_b of the sample's CA against the ground truth's over the same
     residues, the alignment search protein_metrics itself runs (tmtools.tm_align; agreement with its values is not verified).
     shape=True adds the reference's SHAPE_METRICS and non_coil_percent (SHAPE_COLUMNS; secondary_structure without a proline
-    mask, as the backbone carries no sequence).  One device-to-host copy."""
+    mask, as the backbone carries no sequence).  violations=True adds VIOLATION_COLUMNS: the reference's INTER_VIOLATION_METRICS
+    (bonds_c_n_loss_mean, angles_ca_c_n_loss_mean, clashes_mean_loss), angles_c_n_ca_loss_mean and the violation fractions, from
+    fd_violations with the position in the padded chain as the residue number.  One device-to-host copy."""
     B, N = atom37.shape[:2]
     res_mask = res_mask.reshape(B, N).to(torch.float32)
     fixed = torch.zeros_like(res_mask) if fixed_mask is None else fixed_mask.reshape(B, N).to(torch.float32)
@@ -466,6 +540,9 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape
     if shape:
         shape_at = sum(c.shape[1] for c in cols)
         cols.append(_dssp_call(atom37, res_mask, None)[1])
+    if violations:
+        viol_at = sum(c.shape[1] for c in cols)
+        cols.append(_violations_call(atom37, res_mask, None, False)[0])
     host = torch.cat(cols, dim=1).cpu()
     rows = []
     for b in range(B):
@@ -482,5 +559,7 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape
                 row["tm_score_to_gt"] = v[21 + TM_SLOTS.index("tm_score")]
         if shape:
             row.update({name: v[shape_at + SHAPE_SLOTS.index(name)] for name in SHAPE_COLUMNS})
+        if violations:
+            row.update({name: v[viol_at + VIOLATION_SLOTS.index(name)] for name in VIOLATION_COLUMNS})
         rows.append(row)
     return rows

@@ -60,9 +60,11 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
     geometry, clashes, peptide bonds, radius of gyration) from ONE launch issued after the loop, outside the captured step; the
     steps themselves launch what they launch without it.  metrics="shape": metrics also gains metrics.secondary_structure's
     SHAPE_SLOTS (helix, strand and coil fractions, mdtraj's radius of gyration, ...) and ss, the int8 letters codes [B,N], from two
-    more launches issued at the same place."""
-    if isinstance(metrics, str) and metrics != "shape":
-        raise ValueError(f"metrics={metrics!r}: expected False, True or 'shape'")
+    more launches issued at the same place.  metrics="violations": metrics gains metrics.violations' VIOLATION_SLOTS (the bond, angle
+    and clash losses and the violation fractions) instead, from fd_violations' two launches.  metrics="all": backbone + shape +
+    violations."""
+    if isinstance(metrics, str) and metrics not in ("shape", "violations", "all"):
+        raise ValueError(f"metrics={metrics!r}: expected False, True, 'shape', 'violations' or 'all'")
     if record not in (None, "reference", "prot"):
         raise ValueError(f"record={record!r}: expected None, 'reference' or 'prot'")
     if record == "reference" and return_traj:
@@ -273,9 +275,11 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
     if metrics:
         from . import metrics as _metrics
         res["metrics"] = _metrics.backbone_metrics(atom37, st["res_mask"])
-        if metrics == "shape":
+        if metrics in ("shape", "all"):
             shp = _metrics.secondary_structure(atom37, st["res_mask"])
             res["metrics"].update({k: shp[k] for k in _metrics.SHAPE_SLOTS + ("ss",)})
+        if metrics in ("violations", "all"):
+            res["metrics"].update(_metrics.violations(atom37, st["res_mask"]))
     return res
 
 

@@ -1015,6 +1015,72 @@ int fd_dssp_assign(const float* atoms, long atom_stride, int natoms, const float
 int fd_violations(const float* atoms, long atom_stride, const float* res_mask, const int* res_index, int B, int N, double* ws,
                   double* out, double* res_loss, double* atom_loss, unsigned char* flags, void* stream);
 
+/* ---- clustering of a sampled set: linkage, flat cut, diversity (se3_diffusion_amd/csrc/fd_cluster.hip) ----
+ * The diversity of a FrameDiff sampling run is the number of clusters divided by the number of samples, from hierarchical
+ * clustering of the pairwise TM-scores at 0.5; the paper takes it from the MaxCluster program with average linkage.  Here: the
+ * agglomerative clustering of G similarity or distance matrices where they lie in HBM, one thread block per matrix, and the cut of
+ * the tree into flat clusters with a representative each.  NOT verified: the reference repository holds no clustering code, and
+ * MaxCluster exists on no machine this project is built on, so agreement with the clusters or centroids MaxCluster prints has never
+ * been checked; the tests check a float64 restatement of the text below and a recorded run of scipy.cluster.hierarchy (an
+ * independent implementation: a minimum spanning tree for single linkage, nearest-neighbour chains for the other two) on matrices
+ * without ties.  The inclusive cut and the tie rule are this project's own choices; scipy defines neither.
+ *
+ * mat: problem g is the fp64 matrix at mat + g problem_stride, row i at + i ld doubles (ld >= M), read in place.  Only the strict
+ * upper triangle (i < j) of the present samples is read; the diagonal, the lower triangle and the rows and columns of absent
+ * samples may hold anything.  present (optional) [G,M] uint8: sample i of problem g takes part iff it is non-zero; NULL: all do.
+ * kind 0: the entries are distances; kind 1: similarities, and the distance is 1.0 - s, taken in fp64 when the entry is first
+ * read.  A NaN distance is read as +inf.  method 0 single, 1 average (UPGMA), 2 complete.
+ *
+ * fd_cluster_linkage(..): with n present samples, the leaves are the present samples, leaf i having id i (its ORIGINAL position),
+ * size 1.  For s = 0 .. n-2:
+ *   1. among the pairs of active clusters take the one with the smallest key (d, smaller id, larger id), compared in that order;
+ *      x is its cluster of the smaller id, y the other;
+ *   2. Z[g][s] = (id x, id y, d(x, y), size x + size y); x and y leave, and the cluster of id M + s and that size becomes active;
+ *   3. its distance to every other active cluster k (Lance-Williams), n_x = size x, n_y = size y:
+ *        single    d(x, k) < d(y, k) ? d(x, k) : d(y, k)      -- written so that it is min(d(x, k), d(y, k))
+ *        complete  the larger of the two
+ *        average   (n_x d(x, k) + n_y d(y, k)) / (n_x + n_y), each product rounded, then the sum, then the quotient
+ * The three methods are monotone: up to the rounding of the average the heights Z[..][2] never decrease.  Z [G, M-1, 4] fp64;
+ * rows n-1 .. M-2 (all rows if n <= 1) are filled with (-1, -1, +inf, 0); num_merges[g] (int32) = max(n - 1, 0).  Because the ids
+ * of the leaves are original positions and M + s is above them all, a problem with absent samples gives bit for bit what the
+ * compacted problem gives, with leaf c of the compacted problem read as the c-th present sample and n' + s as M + s.
+ * ws: FD_CLUSTER_WS_DOUBLES(M) doubles per problem, G of them, 8-byte aligned, need not be initialised: the working matrix (at the
+ * sizes that matter it stays in L2).  On return the first double of a problem's workspace holds the number of cache rows the
+ * problem rescanned (a cost figure for tools/measure_cluster_cost.py, nothing else may be read from ws).
+ * M <= FD_CLUSTER_MAX_M = 4096: the per-row caches in LDS (best partner's distance and slot, cluster size, id, alive flag) take 84 KB
+ * there, the list of rows to rescan 8 KB more, and the workspace of one problem 128 MB.
+ *
+ * fd_cluster_cut(..): the flat clusters at height cut, from Z and num_merges as fd_cluster_linkage wrote them and the same mat, ld,
+ * problem_stride, present, M and kind.  The written merges with height <= cut are replayed (INCLUSIVE: for similarities the
+ * caller passes cut = 1 - threshold, so that "similarity >= threshold" merges); a cluster is what they join.
+ *   labels [G,M] int32   the cluster of every sample; the clusters are numbered 0 .. K-1 in ascending order of their smallest
+ *                        member; -1 for an absent sample.
+ *   rep [G,M] int32      rep[g][k], k < K: the medoid of cluster k -- the member whose sum of ORIGINAL entries mat[min(i, j)][max(i, j)]
+ *                        against the other members j, added in ascending j, is the largest (kind 1) or the smallest (kind 0);
+ *                        equal sums go to the smallest index; a singleton is its own medoid.  -1 for k >= K.
+ *   out[g][0..FD_CLUSTER_SLOTS) =
+ *     0 num_samples           n
+ *     1 num_clusters          K
+ *     2 diversity             K / n; NaN if n == 0 (a mean over nothing is NaN, as in fd_backbone_metrics)
+ *     3 largest_cluster       members of the largest cluster (0 if n == 0)
+ *     4 num_singletons
+ *     5 mean_within_cluster   the mean original entry over the pairs i < j of one cluster: for every sample i the entries against
+ *                             the members j > i of its cluster added in ascending j, those sums added in ascending i, divided by
+ *                             the number of such pairs; NaN if there is none
+ *     6 last_height_below_cut   the largest written height <= cut; NaN if none
+ *     7 first_height_above_cut  the smallest written height > cut; NaN if none -- the two say how close the cut came to a merge
+ * Both: G == 0 or M == 0 returns FD_OK without a launch and writes nothing.  One launch each, one block per problem, no host
+ * synchronisation, no communication between blocks, no floating-point atomics, every sum in a fixed order: results are bitwise
+ * reproducible and bitwise independent of G and of the problem's place in the batch.  Refused before any launch: M above the limit,
+ * an unknown kind or method, a NaN cut, ld < M, a null or misaligned operand. */
+#define FD_CLUSTER_MAX_M 4096
+#define FD_CLUSTER_SLOTS 8
+#define FD_CLUSTER_WS_DOUBLES(M) ((long)(M) * (long)(M))
+int fd_cluster_linkage(const double* mat, long ld, long problem_stride, const unsigned char* present, int G, int M, int kind,
+                       int method, double* ws, double* Z, int* num_merges, void* stream);
+int fd_cluster_cut(const double* Z, const int* num_merges, const double* mat, long ld, long problem_stride,
+                   const unsigned char* present, int G, int M, int kind, double cut, int* labels, int* rep, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,16 @@ construction for a backbone built from ideal geometry), so violations_per_residu
 and clash masks only.  Still not here: that within-residue term and the OpenMM relaxation itself, solvent
 accessibility, and the sheet-label and bridge-partner columns of a DSSP record.
 
+linkage / cluster / diversity / novelty: the two set-level figures of a sampling run.  diversity is the number of clusters over the
+number of samples, from hierarchical clustering of the pairwise TM-scores at 0.5 (the paper: MaxCluster, average linkage); here
+fd_cluster_linkage (single, average or complete linkage of a similarity or distance matrix where it lies in HBM, one block per
+matrix) and fd_cluster_cut (flat clusters, medoids, counts; include/fd_hip.h is the specification).  novelty is the highest
+TM-score of a sample against a structure library, from tm_align_matrix.  Verified: a float64 restatement of the specification,
+ties included, and a recorded run of scipy.cluster.hierarchy on matrices without ties (tests/golden/cluster.npz).  NOT verified:
+the reference repository holds no clustering code and MaxCluster is not available where this project is built, so agreement
+with the clusters or centroids MaxCluster prints has never been checked.  The inclusive cut (similarity >= threshold merges) and
+the tie rule (smallest height, then smaller id, then larger id) are this project's own choices.
+
 Every value stays on the device as float64; only eval_rows copies to the host, once.
 """
 from __future__ import annotations
@@ -69,6 +79,11 @@ VIOLATION_COLUMNS = ("bonds_c_n_loss_mean", "angles_ca_c_n_loss_mean", "clashes_
                      "violations_per_residue", "num_residue_violations")
 VIOLATIONS_MAX_N = 2048  # FD_VIOLATIONS_MAX_N: fd_violations keeps the five atoms of a whole chain in LDS (140 KB of a CU's 160 KB)
 VIOLATIONS_TILE = 64     # FD_VIOLATIONS_TILE
+CLUSTER_SLOTS = ("num_samples", "num_clusters", "diversity", "largest_cluster", "num_singletons", "mean_within_cluster",
+                 "last_height_below_cut", "first_height_above_cut")
+CLUSTER_MAX_M = 4096     # FD_CLUSTER_MAX_M: the per-row caches of fd_cluster_linkage in LDS (92 KB), 128 MB of workspace per matrix
+CLUSTER_METHODS = {"single": 0, "average": 1, "complete": 2}
+CLUSTER_KINDS = {"distance": 0, "similarity": 1}
 SS_LETTERS = " HBEGITS"  # fd_dssp_assign's codes 0..7 (-1: the residue is absent)
 CA = 1                   # slot of CA in atom37 / the compact [.,5,3] order N, CA, C, CB, O
 
@@ -563,3 +578,118 @@ def eval_rows(atom37, res_mask, fixed_mask=None, gt_atom37=None, tm=False, shape
             row.update({name: v[viol_at + VIOLATION_SLOTS.index(name)] for name in VIOLATION_COLUMNS})
         rows.append(row)
     return rows
+
+
+def _cluster_operands(mat, present, method, kind, who):
+    """(mat addressable in place, present uint8 [G,M] or None, G, M, ld, problem_stride, method code, kind code, batched); every
+    refusal is raised here, before anything is launched or copied"""
+    if method not in CLUSTER_METHODS:
+        raise ValueError(f"{who}: method = {method!r}, expected one of {sorted(CLUSTER_METHODS)}")
+    if kind not in CLUSTER_KINDS:
+        raise ValueError(f"{who}: kind = {kind!r}, expected one of {sorted(CLUSTER_KINDS)}")
+    if mat.dim() not in (2, 3) or mat.shape[-1] != mat.shape[-2]:
+        raise ValueError(f"{who}: a matrix of shape {tuple(mat.shape)}: expected [M,M] or [G,M,M]")
+    batched = mat.dim() == 3
+    if not batched:
+        mat = mat[None]
+        present = None if present is None else present[None]
+    G, M = mat.shape[:2]
+    if M > CLUSTER_MAX_M:
+        raise ValueError(f"{who}: M = {M} samples, at most {CLUSTER_MAX_M} are supported")
+    if present is not None and tuple(present.shape) != (G, M):
+        raise ValueError(f"{who}: present of shape {tuple(present.shape)}, expected {(G, M) if batched else (M,)}")
+    in_place = mat.dtype == torch.float64 and (M <= 1 or (mat.stride(2) == 1 and mat.stride(1) >= M)) and (G <= 1 or mat.stride(0) >= 0)
+    if not in_place:
+        mat = mat.to(torch.float64).contiguous()
+    if present is not None:
+        present = (present != 0).to(torch.uint8).contiguous()
+    ld = mat.stride(1) if M > 1 else max(M, 1)
+    return mat, present, G, M, ld, (mat.stride(0) if G > 1 else 0), CLUSTER_METHODS[method], CLUSTER_KINDS[kind], batched
+
+
+def _linkage_call(mat, present, G, M, ld, stride, method, kind):
+    dev = mat.device
+    Z = torch.empty((G, max(M - 1, 0), 4), dtype=torch.float64, device=dev)
+    num = torch.zeros((G,), dtype=torch.int32, device=dev)          # (zeros: nothing is launched for M == 0)
+    ws = torch.empty((max(1, G * M * M),), dtype=torch.float64, device=dev)      # FD_CLUSTER_WS_DOUBLES
+    hip.get_lib().call("fd_cluster_linkage", mat, ld, stride, present, G, M, kind, method, ws, Z, num)
+    return Z, num, ws
+
+
+def linkage(mat, present=None, method="average", kind="distance"):
+    """Agglomerative clustering (fd_cluster_linkage; include/fd_hip.h is the specification) of a float64 matrix mat [M,M] or of G of
+    them [G,M,M], read in place at any row and problem stride with unit inner stride; only the strict upper triangle is read.
+    kind "distance" or "similarity" (distance = 1 - s); method "single", "average" (UPGMA) or "complete"; present [M] / [G,M]:
+    the samples that take part.  dict Z (float64 [G,M-1,4], or [M-1,4]: smaller id, larger id, height, size per merge; leaf ids are
+    positions, merge s makes id M + s; rows beyond num_merges hold -1, -1, +inf, 0) and num_merges (int32 [G] or 0-d).  Ties go to
+    the smallest (height, smaller id, larger id).  M <= 4096, or ValueError before anything is launched.  One launch, one block
+    per matrix, no host synchronisation."""
+    mat, present, G, M, ld, stride, method, kind, batched = _cluster_operands(mat, present, method, kind, "linkage")
+    Z, num, _ = _linkage_call(mat, present, G, M, ld, stride, method, kind)
+    return {"Z": Z if batched else Z[0], "num_merges": num if batched else num[0]}
+
+
+def cluster(mat, threshold=0.5, method="average", present=None, kind="similarity"):
+    """Flat clusters of mat (as linkage takes it) at a threshold: linkage, then fd_cluster_cut.  For kind "similarity" two clusters
+    merge while their linkage similarity is >= threshold (the cut is 1 - threshold, inclusive); for "distance" threshold is the
+    distance cut itself, inclusive.  dict: labels (int32 [G,M] or [M]: clusters numbered by their smallest member, -1 absent),
+    representatives (int32, same shape: the medoid of cluster k at position k -- the member of the largest summed similarity, or
+    the smallest summed distance, to the others, the smallest index on ties -- and -1 beyond the last cluster), Z and num_merges
+    as linkage returns them, and a float64 tensor [G] (0-d without G) per name of CLUSTER_SLOTS; diversity is num_clusters /
+    num_samples, the figure of a sampling run at similarity = TM-score and threshold 0.5.  Agreement with MaxCluster is NOT
+    verified (include/fd_hip.h).  Two launches, no host synchronisation."""
+    mat, present, G, M, ld, stride, method, kind, batched = _cluster_operands(mat, present, method, kind, "cluster")
+    cut = 1.0 - float(threshold) if kind == 1 else float(threshold)
+    if cut != cut:
+        raise ValueError("cluster: the threshold is NaN")
+    dev = mat.device
+    Z, num, _ = _linkage_call(mat, present, G, M, ld, stride, method, kind)
+    labels = torch.empty((G, M), dtype=torch.int32, device=dev)
+    rep = torch.empty((G, M), dtype=torch.int32, device=dev)
+    if M == 0:
+        # nothing is launched without samples: no clusters, and a mean over nothing is NaN
+        out = torch.full((G, 8), float("nan"), dtype=torch.float64, device=dev)
+        out[:, [0, 1, 3, 4]] = 0.0
+    else:
+        out = torch.empty((G, 8), dtype=torch.float64, device=dev)
+        hip.get_lib().call("fd_cluster_cut", Z, num, mat, ld, stride, present, G, M, kind, cut, labels, rep, out)
+    pick = (lambda x: x) if batched else (lambda x: x[0])
+    res = {"labels": pick(labels), "representatives": pick(rep), "Z": pick(Z), "num_merges": pick(num)}
+    res.update({name: pick(out[:, k]) for k, name in enumerate(CLUSTER_SLOTS)})
+    return res
+
+
+def diversity(pos, mask=None, threshold=0.5, method="average", tm="given", symmetrize="min"):
+    """Diversity of M sampled backbones pos [M,N,3] (mask [M,N]): cluster() of their pairwise TM-scores at `threshold`; the headline
+    figure is the returned diversity = num_clusters / num_samples.  tm="given": pairwise_tm(pos, mask), the TM-score under the
+    position-to-position correspondence (samples of one length).  tm="align": tm_align_matrix(pos, mask), for chains of different
+    lengths (mask marks the padding); its two normalisations are combined elementwise by symmetrize: "min" (the default: the score
+    normalised by the longer chain, the conservative choice), "max" or "mean".  Returns cluster's dict plus tm, the matrix that
+    was clustered.  No host synchronisation."""
+    if tm not in ("given", "align"):
+        raise ValueError(f"diversity: tm = {tm!r}, expected 'given' or 'align'")
+    if symmetrize not in ("min", "max", "mean"):
+        raise ValueError(f"diversity: symmetrize = {symmetrize!r}, expected 'min', 'max' or 'mean'")
+    if method not in CLUSTER_METHODS:
+        raise ValueError(f"diversity: method = {method!r}, expected one of {sorted(CLUSTER_METHODS)}")
+    if pos.dim() != 3 or pos.shape[0] > CLUSTER_MAX_M:
+        raise ValueError(f"diversity: points of shape {tuple(pos.shape)}: expected [M,N,3] with M <= {CLUSTER_MAX_M}")
+    if tm == "given":
+        mat = pairwise_tm(pos, mask)
+    else:
+        both = tm_align_matrix(pos, mask)
+        a, b = both["tm_norm_a"], both["tm_norm_b"]
+        mat = torch.minimum(a, b) if symmetrize == "min" else torch.maximum(a, b) if symmetrize == "max" else 0.5 * (a + b)
+    res = cluster(mat, threshold=threshold, method=method, kind="similarity")
+    res["tm"] = mat
+    return res
+
+
+def novelty(pos, mask, lib_pos, lib_mask):
+    """Novelty of M sampled backbones against a structure library: for every sample the highest TM-score, normalised by the sample's
+    own length, of tm_align_matrix(pos, mask, lib_pos, lib_mask) over the library's chains.  dict max_tm_to_library (float64 [M]) and
+    nearest (int64 [M], the library chain that attains it).  Plain tensor arithmetic on tm_align_matrix's result."""
+    if lib_pos.dim() != 3 or lib_pos.shape[0] == 0:
+        raise ValueError("novelty: the library is empty")
+    best, arg = tm_align_matrix(pos, mask, lib_pos, lib_mask)["tm_norm_a"].max(dim=1)
+    return {"max_tm_to_library": best, "nearest": arg}

@@ -1081,6 +1081,74 @@ int fd_cluster_linkage(const double* mat, long ld, long problem_stride, const un
 int fd_cluster_cut(const double* Z, const int* num_merges, const double* mat, long ld, long problem_stride,
                    const unsigned char* present, int G, int M, int kind, double cut, int* labels, int* rep, double* out, void* stream);
 
+/* ---- chain store: training batches from backbone atoms (se3_diffusion_amd/csrc/fd_chains.hip) ----
+ * What the reference's PdbDataset does per example on the host before it noises it (data/pdb_data_loader.py:133-276:
+ * du.parse_chain_feats, data/utils.py:436-445; the modeled_idx trim, :137-143; the backbone group of atom37_to_frames,
+ * openfold/data/data_transforms.py:755-891, read as Rigid.from_tensor_4x4(rigidgroups_gt_frames)[:, 0], pdb_data_loader.py:240-241;
+ * slots 0..2 of atom37_to_torsion_angles, data_transforms.py:922-1083; seq_idx, :156-168; du.pad_feats), for the entries of one
+ * batch in one launch, from a store of single chains packed once.  The training step reads rigids_0, psi, res_mask and seq_idx of
+ * this (model/score_network.py:201, experiments/train_se3_diffusion.py:561,611-615) and the ground-truth atoms, which the reference
+ * recomputes from rigids_0 and psi (compute_backbone); side chains, aatype, the atom14 arrays and chain_idx are not produced.
+ * NOT du.rigid_frames_from_all_atom (Rigid.from_3_points(N, CA, C)): that is another frame.
+ *
+ * The store (device, contiguous):
+ *   atoms [T,4,3] fp32       N, CA, C, O of all chains, one after the other
+ *   atom_mask [T,4] uint8    non-zero: the atom is present.  The coordinates of an absent atom may hold anything.
+ *   res_index [T] int32      residue numbers
+ *   offsets [C+1] int64      chain c is the residues offsets[c] .. offsets[c+1]-1; ascending, chains below 2^31 residues
+ * A residue is PRESENT when N, CA and C are all present.
+ *
+ * fd_chain_windows(..): window [C,3] int32 = {first present residue, last present residue, number present} of every chain, as
+ * positions within the chain; a chain without a present residue gets {0, -1, 0}.  [first, last] is the reference's modeled_idx
+ * trim; last - first + 1 is its modeled_seq_len.  One block per chain, integer min / max / sum only.  atoms is not read.
+ *
+ * fd_chain_batch(..): entry b of the batch is chain ids[b] (ids [B] int32 on the device; repeats allowed).  Rows 0 .. last - first
+ * of an entry are the residues first .. last of its chain (the WINDOW); the rows behind them are padding.  The caller checks, from
+ * the window table it read back once, that 0 <= ids[b] < C and that no window is longer than Npad, and refuses the call otherwise:
+ * the entry point cannot read device memory.  (The kernel never reads or writes past a buffer whatever the tables hold: a longer
+ * window is cut at Npad, a negative id or an inconsistent window gives an entry of padding.)  All arithmetic after the fp32 loads
+ * is fp64, rounded to fp32 once, where a value is stored.  Sums run left to right, ((a + b) + c) + d.
+ *   centre     c = S / (n + 1e-5), S = the sum of the present CA atoms of the window, n their number (utils.py:439-441).  Thread t
+ *              of 256 adds the rows t, t + 256, ... in that order; the 64 partials of a wave are combined by the butterfly
+ *              v += v[lane ^ o], o = 32, 16, 8, 4, 2, 1; the four wave sums as (s0 + s1) + (s2 + s3).  n is an integer sum.
+ *   atoms      every atom of the window becomes p - c if it is present and the origin if it is not (utils.py:441-443); the residue
+ *              before row 0 is all origin (data_transforms.py:957-965 after the trim).
+ *   gs(p, q, r)  e0 = (q - p) / sqrt(|q - p|^2 + 1e-8); v = r - q; e1' = v - e0 (e0 . v); e1 = e1' / sqrt(|e1'|^2 + 1e-8);
+ *              e2 = e0 x e1  (rigid_utils.py:1233-1275 from_3_points(p_neg_x_axis = p, origin = q, p_xy_plane = r))
+ *   frame      of a present residue: (x, y, z) = gs(CA, C, N), i.e. x = unit(C - CA), y = unit((N - CA) - x (x . (N - CA))),
+ *              z = x x y; the rotation has the columns x, y, z and the translation is CA.  (The reference builds
+ *              from_3_points(C, CA, N) and composes diag(-1, 1, -1): the same matrix.)
+ *   quaternion t0 = 1 + R00 + R11 + R22, t1 = 1 + R00 - R11 - R22, t2 = 1 - R00 + R11 - R22, t3 = 1 - R00 - R11 + R22; the largest
+ *              decides (the first on ties):
+ *                t0: (t0, R21 - R12, R02 - R20, R10 - R01)      t1: (R21 - R12, t1, R01 + R10, R02 + R20)
+ *                t2: (R02 - R20, R01 + R10, t2, R12 + R21)      t3: (R10 - R01, R02 + R20, R12 + R21, t3)
+ *              divided by its norm sqrt(w^2 + x^2 + y^2 + z^2), and negated if w < 0.  No eigen-solve.
+ *   torsions   of the atoms (a, b, c, d): (e0, e1, e2) = gs(b, c, a); w = d - c; ry = e1 . w, rz = e2 . w;
+ *              (sin, cos) = (rz, ry) / sqrt(rz^2 + ry^2 + 1e-8).  Slot 0 pre-omega (CA-1, C-1, N, CA), slot 1 phi (C-1, N, CA, C),
+ *              slot 2 psi (N, CA, C, O) with both entries negated (data_transforms.py:1063-1065); slots 3..6 zero.  Every row of the
+ *              window has them, from the masked atoms, as the reference has.
+ *   outputs    rigids_0 [B,Npad,7] = (w, x, y, z, CA) of a present residue and (1, 0, 0, 0, 0, 0, 0) of every other row;
+ *              torsions [B,Npad,7,2], zero in the padding; res_mask [B,Npad] = 1 where the residue is present, else 0;
+ *              seq_idx [B,Npad] int64 = res_index - (the smallest res_index of the window) + 1 (pdb_data_loader.py:167-168 for one
+ *              chain), 0 in the padding; gt_bb [B,Npad,5,3] (optional) = N, CA, C, CB, O of fd_backbone_atoms on the rows of
+ *              rigids_0 and the psi written here, bit for bit (the same device code), so the loss needs no launch of its own.
+ *              head_const: the constants of fd_backbone_atoms; may be NULL without gt_bb.  Every element is written.
+ * Three deliberate differences from the reference:
+ *   res_mask         the reference's res_mask is the CA mask alone (utils.py:438), which leaves the degenerate frame of a residue
+ *                    without N or C switched on.  Here a residue counts when N, CA and C are present.
+ *   absent rows      the reference's rigids_0 of an absent residue is an arbitrary eigenvector of a zero matrix
+ *                    (Rotation.get_quats -> rot_to_quat's eigh), and zeros in the padding.  Here both are the identity frame at
+ *                    the origin behind res_mask = 0.
+ *   quaternion sign  the reference's sign is whatever eigh returns.  Here w >= 0.
+ * One block of 256 threads per entry, no host synchronisation, no floating-point atomics: results are bitwise reproducible and
+ * bitwise independent of B, of the entry's place in the batch, of Npad and of the residues outside the window.  B == 0 or
+ * Npad == 0 (C == 0 for the windows) returns FD_OK without a launch.  Refused before any launch: a negative size, a null or
+ * misaligned operand, gt_bb without head_const. */
+int fd_chain_windows(const float* atoms, const unsigned char* atom_mask, const long* offsets, int C, int* window, void* stream);
+int fd_chain_batch(const float* atoms, const unsigned char* atom_mask, const int* res_index, const long* offsets, const int* window,
+                   const int* ids, int B, int Npad, const FdHeadConst* head_const, float* rigids_0, float* torsions,
+                   float* res_mask, long* seq_idx, float* gt_bb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,181 @@
+"""Chain store: training batches from backbone atoms, built on the device.
+
+The reference's PdbDataset (data/pdb_data_loader.py:133-276) turns one pickled chain at a time into a training example on the
+host: du.parse_chain_feats centres it on CA, the OpenFold transforms give frames and torsion angles, a scipy/numpy
+forward_marginal noises it, and the DataLoader pads, collates and copies.  Here the chains are packed and uploaded ONCE
+(``ChainStore.freeze``), and a batch is two launches on what lies there: fd_chain_batch (include/fd_hip.h: centre, backbone frame,
+quaternion, pre-omega / phi / psi, res_mask, seq_idx, padding and the ground-truth backbone atoms of the loss) and the existing
+fd_forward_marginal_batch (``SE3Diffuser.forward_marginal_batch``).  Nothing is read back from the device after ``freeze``.
+
+    store = ChainStore("cuda")
+    for feats in my_chains:                      # the dicts process_pdb_dataset.py pickles, or atoms [L,4,3] = N, CA, C, O
+        store.add(feats)
+    store.freeze()
+    for batch, gt_atom37 in store.batches(32, 500_000, np.random.default_rng(0), diffuser, with_gt=True):
+        loss = dsm_loss(batch, model(batch), gt_atom37)
+
+What the training step reads of a chain is rigids_0, psi, res_mask, fixed_mask, seq_idx, sc_ca_t and the outputs of
+forward_marginal (model/score_network.py:201, experiments/train_se3_diffusion.py:561,611-615); that is what a batch holds, under
+the keys of the reference's DataLoader (those of ``train_step.synthetic_batch``).
+
+Out of scope: entries of several chains and chain_idx; aatype, side-chain torsions and the atom14 arrays; the evaluation branch of
+the dataset (t = 1, sample_ref(impute=...)); motif masks (PdbDataset._create_diffused_masks, which its own __getitem__ never
+calls: fixed_mask is zero); reading pickles, mmCIF or PDB files -- ``add`` takes arrays.
+
+Three deliberate differences from the reference (include/fd_hip.h): res_mask needs N, CA and C, not CA alone; the frame of an
+absent residue and of a padding row is the identity at the origin behind res_mask = 0; quaternions have w >= 0.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import hip
+
+_BACKBONE37 = (0, 1, 2, 4)                        # N, CA, C, O in atom37 order (residue_constants.atom_order)
+_BATCH_KEYS = ("res_mask", "fixed_mask", "seq_idx", "t", "sc_ca_t", "rigids_t", "rigids_0", "torsion_angles_sin_cos", "rot_score",
+               "trans_score", "rot_score_scaling", "trans_score_scaling")
+
+
+class ChainStore:
+    """Backbone atoms of single chains, packed on `device`: atoms [T,4,3] fp32 (N, CA, C, O), atom_mask [T,4] uint8,
+    res_index [T] int32, offsets [C+1] int64 -- the operands of fd_chain_windows / fd_chain_batch."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._pending = []
+        self._frozen = False
+        self.windows = None
+
+    # ------------------------------------------------------------------ building
+    def add(self, chain=None, *, atoms=None, atom_mask=None, residue_index=None) -> int:
+        """One chain; returns its id.  `chain` is the dict tools of the reference pickle (process_pdb_dataset.py: atom_positions
+        [L,37,3], atom_mask [L,37], residue_index [L]; the atom37 columns 0, 1, 2, 4 are taken) or a dict / keywords with atoms
+        [L,4,3] = N, CA, C, O, atom_mask [L,4] and residue_index [L] (None: 0 .. L-1)."""
+        if self._frozen:
+            raise RuntimeError("ChainStore.add after freeze()")
+        if chain is not None:
+            if "atom_positions" in chain:
+                pos, msk = np.asarray(chain["atom_positions"]), np.asarray(chain["atom_mask"])
+                if pos.ndim != 3 or pos.shape[1:] != (37, 3) or msk.shape != pos.shape[:2]:
+                    raise ValueError(f"expected atom_positions [L,37,3] and atom_mask [L,37], got {pos.shape} and {msk.shape}")
+                atoms, atom_mask = pos[:, _BACKBONE37], msk[:, _BACKBONE37]
+            else:
+                atoms, atom_mask = chain["atoms"], chain["atom_mask"]
+            residue_index = chain.get("residue_index", residue_index)
+        atoms = np.asarray(atoms, dtype=np.float32)
+        if atoms.ndim != 3 or atoms.shape[1:] != (4, 3):
+            raise ValueError(f"expected atoms [L,4,3] (N, CA, C, O), got {atoms.shape}")
+        L = atoms.shape[0]
+        atom_mask = np.asarray(atom_mask)
+        if atom_mask.shape != (L, 4):
+            raise ValueError(f"expected atom_mask [{L},4], got {atom_mask.shape}")
+        residue_index = np.arange(L) if residue_index is None else np.asarray(residue_index)
+        if residue_index.shape != (L,):
+            raise ValueError(f"expected residue_index [{L}], got {residue_index.shape}")
+        self._pending.append((atoms, (atom_mask != 0).astype(np.uint8), residue_index.astype(np.int32)))
+        return len(self._pending) - 1
+
+    def freeze(self):
+        """Pack, upload, run fd_chain_windows and copy its [C,3] table to the host: the one synchronisation of the store."""
+        if self._frozen:
+            return self
+        C = len(self._pending)
+        lens = np.array([len(a) for a, _, _ in self._pending], dtype=np.int64)
+        cat = lambda k, shape, dt: (np.concatenate([p[k] for p in self._pending]) if C else np.zeros(shape, dt))
+        dev = self.device
+        self.atoms = torch.from_numpy(np.ascontiguousarray(cat(0, (0, 4, 3), np.float32))).to(dev)
+        self.atom_mask = torch.from_numpy(np.ascontiguousarray(cat(1, (0, 4), np.uint8))).to(dev)
+        self.res_index = torch.from_numpy(np.ascontiguousarray(cat(2, (0,), np.int32))).to(dev)
+        self.offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev)
+        self._pending = None
+        window = torch.empty((C, 3), dtype=torch.int32, device=dev)
+        hip.get_lib().call("fd_chain_windows", self.atoms, self.atom_mask, self.offsets, C, window)
+        self._window = window
+        self.windows = window.cpu().numpy()        # {first present, last present, number present} per chain
+        self._frozen = True
+        return self
+
+    def __len__(self):
+        return len(self._pending) if not self._frozen else self.windows.shape[0]
+
+    @property
+    def lengths(self):
+        """host array [C]: residues from the first to the last present one -- the reference's modeled_seq_len; 0 for a chain
+        without a present residue"""
+        self._need_frozen()
+        return (self.windows[:, 1] - self.windows[:, 0] + 1).astype(np.int64)
+
+    def _need_frozen(self):
+        if not self._frozen:
+            raise RuntimeError("ChainStore: call freeze() first")
+
+    # ------------------------------------------------------------------ batches
+    def build_batch(self, ids, n_pad=None, with_gt=True):
+        """fd_chain_batch alone: rigids_0 [B,Npad,7], torsion_angles_sin_cos [B,Npad,7,2], res_mask [B,Npad] (fp32), seq_idx
+        [B,Npad] (int64) and, with_gt, gt_bb [B,Npad,5,3] (N, CA, C, CB, O of compute_backbone(rigids_0, psi)) of the chains
+        `ids` (host integers, repeats allowed), padded to n_pad (None: the longest window among them)."""
+        self._need_frozen()
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        B, C = len(ids), len(self)
+        if B and (ids.min() < 0 or ids.max() >= C):
+            raise ValueError(f"chain ids must lie in [0, {C}), got {ids.min()} .. {ids.max()}")
+        longest = int(self.lengths[ids].max()) if B else 0
+        n_pad = longest if n_pad is None else int(n_pad)
+        if n_pad < longest:
+            raise ValueError(f"n_pad = {n_pad} is shorter than a window of {longest} residues (chain {int(ids[np.argmax(self.lengths[ids])])})")
+        from .. import trunk
+        dev = self.device
+        out = {"rigids_0": torch.empty((B, n_pad, 7), device=dev), "torsion_angles_sin_cos": torch.empty((B, n_pad, 7, 2), device=dev),
+               "res_mask": torch.empty((B, n_pad), device=dev), "seq_idx": torch.empty((B, n_pad), dtype=torch.int64, device=dev)}
+        if with_gt:
+            out["gt_bb"] = torch.empty((B, n_pad, 5, 3), device=dev)
+        dev_ids = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        hip.get_lib().call("fd_chain_batch", self.atoms, self.atom_mask, self.res_index, self.offsets, self._window, dev_ids, B, n_pad,
+                           trunk.head_const(), out["rigids_0"], out["torsion_angles_sin_cos"], out["res_mask"], out["seq_idx"],
+                           out.get("gt_bb"))
+        return out
+
+    def training_batch(self, ids, diffuser, t=None, n_pad=None, noise=None, generator=None, rng=None, min_t=0.01):
+        """(batch, gt_atom37) for the chains `ids`: fd_chain_batch, then diffuser.forward_marginal_batch(rigids_0, t,
+        diffuse_mask=res_mask, noise=, generator=) as it stands (its kernel copies the frame and writes zero scores where the mask
+        is 0).  batch has the keys, dtypes and shapes of train_step.synthetic_batch; fixed_mask and sc_ca_t are zero.  t [B]
+        defaults to rng.uniform(min_t, 1) per entry (pdb_data_loader.py:252; data.min_t = 0.01 in config/base.yaml) -- the same id
+        repeated with different t is the reference's time_batch mode.  gt_atom37 [B,Npad,37,3] holds the five backbone atoms of
+        compute_backbone(rigids_0, psi), atoms 5..36 zero."""
+        built = self.build_batch(ids, n_pad)
+        B, N = built["res_mask"].shape
+        if t is None:
+            rng = np.random.default_rng() if rng is None else rng
+            t = rng.uniform(min_t, 1.0, size=B)
+        t = np.asarray(t, dtype=np.float64).reshape(B)
+        dev = self.device
+        noised = diffuser.forward_marginal_batch(built["rigids_0"], t, diffuse_mask=built["res_mask"], noise=noise, generator=generator)
+        values = dict(built, fixed_mask=torch.zeros((B, N), device=dev), t=torch.tensor(t, dtype=torch.float32, device=dev),
+                      sc_ca_t=torch.zeros((B, N, 3), device=dev), **noised)
+        gt_atom37 = torch.zeros((B, N, 37, 3), device=dev)
+        gt_atom37[:, :, :5] = built["gt_bb"]
+        return {k: values[k] for k in _BATCH_KEYS}, gt_atom37
+
+    def batch_plan(self, batch_size, max_squared_res, rng):
+        """One pass over the store in the reference's length_batch mode, as host arithmetic on `lengths`: a list of id arrays, each
+        of ONE length N and of at most min(batch_size, max_squared_res // N^2) chains (du.length_batching, data/utils.py:387-399),
+        every chain of a length in exactly one of them, chains and batches in an order drawn from rng.  Chains without a present
+        residue, and lengths with N^2 > max_squared_res, are left out."""
+        lengths = self.lengths
+        plan = []
+        for n in np.unique(lengths[lengths > 0]):
+            b = min(int(batch_size), int(max_squared_res) // int(n * n))
+            if b < 1:
+                continue
+            ids = rng.permutation(np.flatnonzero(lengths == n))
+            plan += [ids[k:k + b] for k in range(0, len(ids), b)]
+        return [plan[k] for k in rng.permutation(len(plan))]
+
+    def batches(self, batch_size, max_squared_res, rng, diffuser, with_gt=False, min_t=0.01, generator=None):
+        """Iterator over one pass of batch_plan(batch_size, max_squared_res, rng): device dicts as training_batch returns them (what
+        the reference's train_epoch reads from its DataLoader; its .to(device) is then a no-op), or (batch, gt_atom37) pairs
+        with_gt.  t comes from the same rng, so a seeded rng fixes the whole sequence but for the noise (generator)."""
+        for ids in self.batch_plan(batch_size, max_squared_res, rng):
+            batch, gt = self.training_batch(ids, diffuser, rng=rng, min_t=min_t, generator=generator)
+            yield (batch, gt) if with_gt else batch

@@ -293,6 +293,8 @@ _SIGS = {
     "fd_violations": "plppiippppps",
     "fd_cluster_linkage": "pllp" + "iiii" + "ppps",
     "fd_cluster_cut": "pppllp" + "iii" + "d" + "ppps",
+    "fd_chain_windows": "pppips",
+    "fd_chain_batch": "pppppp" + "ii" + "S" + "ppppp" + "s",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

@@ -1149,6 +1149,89 @@ int fd_chain_batch(const float* atoms, const unsigned char* atom_mask, const int
                    const int* ids, int B, int Npad, const FdHeadConst* head_const, float* rigids_0, float* torsions,
                    float* res_mask, long* seq_idx, float* gt_bb, void* stream);
 
+/* ---- sequence design: ProteinMPNN inference (se3_diffusion_amd/csrc/fd_design.hip) ----
+ * The reference's vanilla (full-backbone) ProteinMPNN (ProteinMPNN/protein_mpnn_utils.py: ProteinFeatures :899-994, EncLayer
+ * :602-647, DecLayer :650-688, ProteinMPNN.forward :1036-1079 and .sample :1083-1168) in eval mode with augment_eps = 0, for single
+ * chains with every residue present (mask = 1, one chain label), hidden_dim = node_features = edge_features = 128, three encoder
+ * and three decoder layers.  Not covered: ca_only, several chains, missing residues, tied_sample, PSSM inputs, bias_by_res,
+ * conditional_probs / unconditional_probs, training.
+ *
+ * Backbones are packed, never padded:
+ *   atoms [T,4,3] fp32       N, CA, C, O of all backbones, one after the other
+ *   res_index [T] int32      residue numbers
+ *   offsets [B+1] int64      backbone b is the rows offsets[b] .. offsets[b+1]-1; at most FD_MPNN_MAX_L rows each (the caller
+ *                            checks: the entry points cannot read device memory; a kernel only looks at the first FD_MPNN_MAX_L)
+ *   chain_of [T] int32       the backbone of every row
+ * K = the checkpoint's k_neighbors (1 .. FD_MPNN_MAX_K); a backbone of L rows uses Ke = min(K, L) neighbours: per-row arrays keep
+ * the stride K and their entries k >= Ke are -1 (E_idx), zero (h_E) or unwritten (EB).
+ * Every product is an fp32 product summed in fp32 (v_mfma_f32_16x16x4_f32 for the per-edge Linears: a k-ordered fmaf chain per
+ * output; fmaf chains for the Linears of one node); exp, log, erf and sqrt are the device's fp32 functions; GELU is the exact one,
+ * 0.5 x (1 + erf(x / sqrt 2)); LayerNorm has eps = 1e-5 and the biased variance.  Nothing is atomic, no sum's order depends on the
+ * other backbones or sequences of the call: a row is bitwise independent of B and of its backbone's place, a sequence of num_seqs.
+ *
+ * The Linears of one node split their inputs into 2, 4 or 8 contiguous slices, one fmaf chain per slice and output, and add the
+ * slices in ascending order.
+ *
+ * Packed weights (fp32, device, contiguous, ew and dw 16-byte aligned; "T" = stored transposed, [in][out], so that a column of
+ * outputs is contiguous):
+ *   gw [FD_MPNN_GRAPH_FLOATS]: mu[16] = linspace(2, 22, 16) | pos[66][16], pos[d] = embeddings.linear.weight[:, d] + its bias |
+ *     edge_embedding.weight T [416][128] | norm_edges weight, bias | W_e.weight T [128][128] | W_e.bias.
+ *   NU (one node update, 148736 floats): W3 T [128][128] | b3 | norm1 weight, bias | dense.W_in T [128][512] | its bias [512] |
+ *     dense.W_out T [512][128] | its bias | norm2 weight, bias.
+ *   ew [FD_MPNN_ENC_FLOATS]: W1.bias of encoder layer 0 [128] | three layers of
+ *     W1[:, 128:256] T | W2 T | b2 | NU | NPW [128][6 x 128] | NPB [6 x 128] | W11[:, 128:256] T | W12 T | b12 | W13 T | b13 |
+ *     norm3 weight, bias.
+ *     NPW / NPB give the NODE PRODUCTS of the layer's new h_V, slots of 128: 0 = W11[:, 0:128] h + b11, 1 = W11[:, 256:384] h; then,
+ *     for layers 0 and 1, 2 = (next layer's W1)[:, 0:128] h + b1, 3 = (next W1)[:, 256:384] h (slots 4, 5 unused), and for layer 2
+ *     2 + l = (decoder layer l's W1)[:, 384:512] h (l = 0, 1, 2), 5 = (decoder layer 0's W1)[:, 0:128] h.
+ *   dw [FD_MPNN_DEC_FLOATS]: (decoder W1)[:, 128:256] T of layers 0, 1, 2 | their three b1 | three layers of
+ *     W1[:, 0:128] T | W1[:, 384:512] T | TS [21][128], TS[a] = W1[:, 256:384] W_s.weight[a] | W2 T | b2 | NU ; then
+ *     W_out.weight T [128][21] | W_out.bias [21].
+ *
+ * fd_mpnn_graph(..): per row i the Ke nearest rows of its backbone by d(i, j) = sqrt(|CA_j - CA_i|^2 + 1e-6) in fp32
+ * (((dx^2 + dy^2) + dz^2) + 1e-6), ascending under the key (d, j): E_idx [T,K] int32 holds positions WITHIN the backbone, the
+ * row itself first (d = 1e-3) unless another CA coincides with it.  h_E [T,K,128] = W_e(norm_edges(edge_embedding([pos ; rbf]))):
+ * pos = pos[clip(res_index[i] - res_index[j] + 32, 0, 64)]; rbf = the 25 sets of 16 exp(-((D - mu) / 1.25)^2) in the reference's
+ * order (:958-982), D = sqrt(|A_i - B_j|^2 + 1e-6), with the virtual CB = -0.58273431 a + 0.56802827 b - 0.54067466 c + CA,
+ * b = CA - N, c = C - CA, a = b x c (:946-949).  One block per row.
+ *
+ * fd_mpnn_encoder(..): the three EncLayers on h_V = 0 (h_V [T,128] is written, not read), h_E in place, and what the decoder needs
+ * per backbone: node [T,6,128] = the node products of layer 2 (above), EB [3,T,K,128] = (decoder layer l's W1)[:, 128:256] h_E +
+ * b1.  W1 [h_i ; e_ik ; h_j] is formed as (A h_i + b1) + B e_ik + C h_j from node products; the node update is
+ * norm1(h_i + (W3 (sum_k g_k) + Ke b3) / 30) with g_k the output of the second GELU, then norm2(x + dense(x)).  node_ws [T,6,128]
+ * is a workspace, distinct from node.  Eight launches (one small, seven of one block per row).
+ *
+ * fd_mpnn_decode(..): one block per (backbone b, sequence s), grid (B, num_seqs).  Arrays over sequences are [num_seqs, T]:
+ * order int32 (order[s, offsets[b] + n] = the position within b decoded n-th; a permutation, which the caller guarantees -- an
+ * entry outside 0 .. L-1 is skipped), S_in int32 letters 0..20, uniforms fp32; fixed [T] uint8 (may be NULL) is per row.  At step n,
+ * position t = order[n]: for each decoder layer l the first Linear of the message of edge k (neighbour j) is
+ *   W1a^l h^l[t] + EB[l][t,k] + (TS^l[S[j]] + W1d^l h^l[j])   if j was decoded before t      (h^0 = the encoder's h_V)
+ *   W1a^l h^l[t] + EB[l][t,k] + W1d^l h^0[j]                  otherwise (t itself included)
+ * then GELU, W2, GELU, the sum over k, W3 behind the sum as in the encoder, norm1, dense, norm2.  After layer 2:
+ * logits = W_out h^3[t]; log_probs[s,t] = log_softmax(logits); p = softmax((logits / temperature - 1e8 omit) + bias / temperature)
+ * (omit, bias [21] fp32).  forced = 0: the letter is the first a with uniforms[s,t] < p_0 + .. + p_a (summed in that order; the
+ * last a with p_a > 0 if there is none), except at rows with fixed != 0, which take S_in and report probs = 0 as the reference's
+ * all_probs does; forced = 1: every letter is S_in (the reference's forward(use_input_decoding_order=True)), uniforms may be NULL.
+ * Outputs: S_out [num_seqs,T] int32, log_probs and probs [num_seqs,T,21].  scratch [num_seqs,T,2,128] fp32 is block-private
+ * working memory (W1d^l h^l[j], l = 1, 2, of the decoded positions).  No barrier across blocks, no atomics.
+ * T == 0 (B == 0, num_seqs == 0) returns FD_OK without a launch.  Refused before any launch: a negative size, K outside
+ * 1 .. FD_MPNN_MAX_K, a null or misaligned operand, temperature <= 0, node == node_ws. */
+#define FD_MPNN_HIDDEN 128
+#define FD_MPNN_MAX_K 64
+#define FD_MPNN_MAX_L 1024
+#define FD_MPNN_NODE_SLOTS 6
+#define FD_MPNN_GRAPH_FLOATS 71088
+#define FD_MPNN_ENC_FLOATS 991232
+#define FD_MPNN_DEC_FLOATS 654357
+int fd_mpnn_graph(const float* atoms, const int* res_index, const long* offsets, const int* chain_of, long T, int K,
+                  const float* gw, int* E_idx, float* h_E, void* stream);
+int fd_mpnn_encoder(const int* E_idx, const long* offsets, const int* chain_of, long T, int K, const float* ew, const float* dw,
+                    float* h_V, float* h_E, float* node, float* node_ws, float* EB, void* stream);
+int fd_mpnn_decode(const int* E_idx, const long* offsets, int B, long T, int K, int num_seqs, const float* dw, const float* h_V,
+                   const float* node, const float* EB, const int* order, const int* S_in, const unsigned char* fixed,
+                   const float* uniforms, const float* omit, const float* bias, float temperature, int forced, float* scratch,
+                   int* S_out, float* log_probs, float* probs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

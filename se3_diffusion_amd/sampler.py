@@ -36,7 +36,8 @@ def _f64(x, dev):
 
 @torch.no_grad()
 def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_condition=True, center=True,
-           generator=None, noise_fn=None, return_traj=False, use_graph=False, stats=None, record=None, metrics=False):
+           generator=None, noise_fn=None, return_traj=False, use_graph=False, stats=None, record=None, metrics=False,
+           design=None, seqs_per_sample=8):
     """Run the reverse process on `feats` (from init_feats).  noise_fn(step, shape) -> (z_rot, z_trans) injects
     draws (e.g. the numpy stream, for trajectory parity); default draws on the device.
     Returns dict(rigids [B,N,7], atom37 [B,N,37,3], psi, (return_traj: rigid_traj, a list of per-step frames)).  `stats` (a dict)
@@ -62,7 +63,12 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
     SHAPE_SLOTS (helix, strand and coil fractions, mdtraj's radius of gyration, ...) and ss, the int8 letters codes [B,N], from two
     more launches issued at the same place.  metrics="violations": metrics gains metrics.violations' VIOLATION_SLOTS (the bond, angle
     and clash losses and the violation fractions) instead, from fd_violations' two launches.  metrics="all": backbone + shape +
-    violations."""
+    violations.
+
+    design=<design.SequenceDesigner>: the result gains design = designer.design(atom37, num_seqs=seqs_per_sample,
+    generator=generator), seqs_per_sample sequences for every backbone (ProteinMPNN at temperature 0.1) from launches issued after
+    the loop; its draws are taken from `generator` behind the trajectory's, so the backbones are those of design=None.  Every
+    residue of every backbone is designed: feats with padding (res_mask == 0) are not supported here."""
     if isinstance(metrics, str) and metrics not in ("shape", "violations", "all"):
         raise ValueError(f"metrics={metrics!r}: expected False, True, 'shape', 'violations' or 'all'")
     if record not in (None, "reference", "prot"):
@@ -280,6 +286,8 @@ def sample(model, diffuser, feats, num_t=500, min_t=0.01, noise_scale=0.1, self_
             res["metrics"].update({k: shp[k] for k in _metrics.SHAPE_SLOTS + ("ss",)})
         if metrics in ("violations", "all"):
             res["metrics"].update(_metrics.violations(atom37, st["res_mask"]))
+    if design is not None:
+        res["design"] = design.design(atom37, num_seqs=seqs_per_sample, generator=generator)
     return res
 
 

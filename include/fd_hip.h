@@ -1232,6 +1232,54 @@ int fd_mpnn_decode(const int* E_idx, const long* offsets, int B, long T, int K, 
                    const float* uniforms, const float* omit, const float* bias, float temperature, int forced, float* scratch,
                    int* S_out, float* log_probs, float* probs, void* stream);
 
+/* ---- PDB text (se3_diffusion_amd/csrc/fd_pdb.hip) ----
+ * The text the reference's analysis/utils.py write_prot_to_pdb writes (data/protein.py to_pdb per frame), byte for byte, from
+ * atom37 coordinates on the device.  M models of N residues x 37 atom slots, fp32; model m is read at atoms + m model_stride
+ * (floats), [N,37,3] contiguous inside a model, so a [T,B,N,37,3] record is formatted per backbone in place.  aatype [N] int32
+ * (NULL: all 0 = ALA), b_factors [N,37] fp32 (NULL: 0), both shared by all models.
+ *
+ * An atom is PRESENT iff (|x| + |y|) + |z| > 1e-7f in fp32.  The file is lines of 80 columns and '\n'; per model
+ *   MODEL     {first_model + m}
+ *   ATOM  {serial:>5} {' ' + name:<4} {res3:>3} A{resnum:>4}    {x:>8.3f}{y:>8.3f}{z:>8.3f}  1.00{b:>6.2f}          {element:>2}
+ *     one per present atom in (residue, slot) order: serial from 1 in each model, name = the slot's atom37 name, res3 the residue
+ *     name of aatype (20 = UNK), resnum the residue's position from 0, element the name's first letter;
+ *   TER   {serial:>5}      {res3:>3} A{resnum:>4}    with the next serial and the LAST residue's name and number;
+ *   ENDMDL
+ * and "END" without a newline behind the last model: 81 (lines_0 + .. + lines_{M-1}) + 3 bytes with lines_m = counts[m] + 3.
+ * Numbers are printed from rint(x 1000) and rint(b 100) in fp64 (exact products: round-half-to-even on the exact value) with the
+ * sign of the sign bit, so -0.0004f prints -0.000.
+ *
+ * fd_pdb_count(..): counts [M] int64 = present atoms per model; status [M] int64 = FD_PDB_STATUS_OK, or for the model's offending
+ * entry of the smallest linear index ((m N + residue) 37 + slot) the word 8 index + kind:
+ *   FD_PDB_NONFINITE  a coordinate of the entry is NaN or infinite (whether or not the rule above calls the atom present);
+ *   FD_PDB_COORD      a coordinate of a present atom rounds to something outside -999.999 .. 9999.999;
+ *   FD_PDB_BFACTOR    the b-factor of a present atom is not finite or rounds to something outside -99.99 .. 999.99;
+ *   FD_PDB_SERIAL     the atom whose serial is 100000; if the model has exactly 99999 atoms, TER's serial is, and the entry is the
+ *                     model's last;
+ *   FD_PDB_LENGTH     N > FD_PDB_MAX_N: entry (m, FD_PDB_MAX_N, 0), the first residue number of five digits;
+ *   FD_PDB_AATYPE     aatype[residue] outside 0 .. 20: entry (0, residue, 0).
+ * An entry with several kinds reports the smallest.  The minimum over status[0 .. M-1] is the file's first offender.  One block
+ * per model, reductions by shuffles in a fixed order, no atomics.
+ *
+ * fd_pdb_format(..): line_offset [M] int64 = the exclusive prefix sum of lines_m; out [out_bytes] with out_bytes = the size
+ * above, 16-byte aligned.  One block per model; the serial is an ordered prefix scan of the presence flags, so two runs write
+ * the same bytes.  Meant for input whose status is OK: otherwise every field still stays inside its columns (digits that do
+ * not fit are dropped, an aatype outside 0 .. 20 prints UNK), and nothing is written outside [0, out_bytes): a run of
+ * lines that would cross either end is left out.  M == 0 returns FD_OK without a launch (the file is then "END", which the
+ * caller writes).  Refused before any launch: N < 1, N x 111 >= 2^30, a negative first_model, a null or misaligned operand. */
+#define FD_PDB_MAX_N 10000
+#define FD_PDB_STATUS_OK 0x7fffffffffffffffL
+#define FD_PDB_NONFINITE 1
+#define FD_PDB_COORD 2
+#define FD_PDB_BFACTOR 3
+#define FD_PDB_SERIAL 4
+#define FD_PDB_LENGTH 5
+#define FD_PDB_AATYPE 6
+int fd_pdb_count(const float* atoms, long model_stride, const int* aatype, const float* b_factors, int M, int N, long* counts,
+                 long* status, void* stream);
+int fd_pdb_format(const float* atoms, long model_stride, const int* aatype, const float* b_factors, const long* line_offset, int M,
+                  int N, long first_model, unsigned char* out, long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

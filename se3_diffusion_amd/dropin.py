@@ -19,6 +19,10 @@ Experiment.inference_fn -- the reference's per-step host loop -- by se3_diffusio
 signature and return value on the device-resident, hipGraph-replayed sampler:
 
     python -m se3_diffusion_amd.dropin --device-inference /path/to/se3_diffusion experiments/inference_se3_diffusion.py
+
+Writing: `install(..., device_pdb=True)` (shell: `--device-pdb`, next to `--device-inference` in either order) binds
+analysis.utils.write_prot_to_pdb -- one f-string per atom on the host -- to se3_diffusion_amd.pdb.write_prot_to_pdb, which formats the
+same bytes on the device.  Sampler.save_traj and Experiment.eval_fn reach it through `au.write_prot_to_pdb`.
 """
 from __future__ import annotations
 
@@ -38,7 +42,7 @@ _RIGID = {"openfold.utils.rigid_utils": "se3_diffusion_amd.openfold.utils.rigid_
 
 
 def install(reference_root: str | None = None, replace_rigid_utils: bool = False, patch_all_atom: bool = True,
-            device_inference: bool = False):
+            device_inference: bool = False, device_pdb: bool = False):
     """Bind the reference's hot-path module paths to the HIP implementations.  Idempotent.
 
     replace_rigid_utils: also bind openfold.utils.rigid_utils to the eigh-free Rigid/Rotation of this
@@ -46,7 +50,10 @@ def install(reference_root: str | None = None, replace_rigid_utils: bool = False
     pipeline uses more of that file, so the default keeps the reference's).
 
     device_inference: import experiments.train_se3_diffusion (after the bindings are in place) and set its
-    Experiment.inference_fn to inference.inference_fn.  Off by default: the reference's own loop stays."""
+    Experiment.inference_fn to inference.inference_fn.  Off by default: the reference's own loop stays.
+
+    device_pdb: set analysis.utils.write_prot_to_pdb to pdb.write_prot_to_pdb (the same signature, file names and bytes), after
+    the bindings above.  Off by default: the reference's own writer stays."""
     if reference_root is not None:
         reference_root = os.path.abspath(reference_root)
         if not os.path.isdir(os.path.join(reference_root, "experiments")):
@@ -75,18 +82,22 @@ def install(reference_root: str | None = None, replace_rigid_utils: bool = False
         from . import inference
         tr = importlib.import_module("experiments.train_se3_diffusion")
         tr.Experiment.inference_fn = inference.inference_fn
+    if device_pdb:
+        from . import pdb
+        importlib.import_module("analysis.utils").write_prot_to_pdb = pdb.write_prot_to_pdb
     return sorted(table)
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    device_inference = bool(argv) and argv[0] == "--device-inference"
-    if device_inference:
-        argv = argv[1:]
+    flags = {"--device-inference": False, "--device-pdb": False}
+    while argv and argv[0] in flags:
+        flags[argv.pop(0)] = True
     if len(argv) < 2:
-        raise SystemExit("usage: python -m se3_diffusion_amd.dropin [--device-inference] <reference_root> <script.py> [args...]")
+        raise SystemExit("usage: python -m se3_diffusion_amd.dropin [--device-inference] [--device-pdb] <reference_root> <script.py> "
+                         "[args...]")
     root, script = argv[0], argv[1]
-    install(root, device_inference=device_inference)
+    install(root, device_inference=flags["--device-inference"], device_pdb=flags["--device-pdb"])
     sys.argv = [script] + argv[2:]
     os.chdir(root)
     runpy.run_path(os.path.join(root, script) if not os.path.isabs(script) else script, run_name="__main__")

@@ -298,6 +298,8 @@ _SIGS = {
     "fd_mpnn_graph": "pppp" + "li" + "ppp" + "s",
     "fd_mpnn_encoder": "ppp" + "li" + "pp" + "ppppp" + "s",
     "fd_mpnn_decode": "pp" + "ilii" + "pppp" + "pppppp" + "fi" + "pppp" + "s",
+    "fd_pdb_count": "plpp" + "ii" + "pp" + "s",
+    "fd_pdb_format": "plppp" + "iil" + "pl" + "s",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

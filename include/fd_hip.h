@@ -1280,6 +1280,67 @@ int fd_pdb_count(const float* atoms, long model_stride, const int* aatype, const
 int fd_pdb_format(const float* atoms, long model_stride, const int* aatype, const float* b_factors, const long* line_offset, int M,
                   int N, long first_model, unsigned char* out, long out_bytes, void* stream);
 
+/* ---- reading PDB text (se3_diffusion_amd/csrc/fd_pdb_read.hip) ----
+ * The inverse of the above: atom37 arrays from the text of F PDB files that lie end to end in text [n] uint8 (16-byte aligned),
+ * file f being the bytes file_offsets[f] .. file_offsets[f+1] (int64 [F+1], 0 first, n last, not decreasing; an empty file holds
+ * no line).  Nothing outside text is read.
+ *
+ * LINES.  A line starts at the first byte of a file and behind every '\n'; it ends in front of the next '\n' or at the end of
+ * its file, and a '\r' directly in front of that end is not part of it.  Its columns are its bytes, from 1; a column behind its
+ * end reads as a blank; columns behind 80 are not looked at.  Lines are numbered from 0 through all files.
+ * RECORDS.  Columns 1-6 decide: "ATOM  ", "HETATM", "ENDMDL" (any other line, MODEL, TER, ANISOU, REMARK among them, only
+ * counts as a line).  The COORDINATE RECORDS are the ATOM lines, and the HETATM lines iff hetatm != 0; with model_all == 0 only
+ * those with no ENDMDL line between the start of their file and themselves.  A model's number is the count of ENDMDL lines
+ * between the start of its file and its records; MODEL lines are not read.  Of a coordinate record (PDB v3.3):
+ *   13-16 atom name: with the blanks at both ends removed, one of the 37 atom37 names gives the slot; any other name (a
+ *         hydrogen, a name with a blank inside) gives none -- the record still counts for its residue;
+ *   18-20 resName -> aatype 0 .. 19 in the order ALA ARG ASN ASP CYS GLN GLU GLY HIS ILE LEU LYS MET PHE PRO SER THR TRP TYR VAL,
+ *         20 for anything else;      22 chainID;      23-26 resSeq, a signed integer;      27 iCode;
+ *   31-38, 39-46, 47-54 x, y, z;     55-60 occupancy (all blank: 1);      61-66 tempFactor (all blank: 0).
+ * NUMBERS.  A field is blanks, an optional sign, digits with at most one '.' among them, blanks; at least one digit.  Its value
+ * is the integer made of the digits divided by 10^(digits behind the point) in fp64, rounded once to fp32: what
+ * float32(float(field)) gives.  resSeq is the same without the point.
+ * RESIDUES.  The key of a coordinate record is (chainID, resSeq, iCode, HETATM or not).  A record begins a RESIDUE ROW unless
+ * the coordinate record before it lies in the same file with no ENDMDL line between the two and has the same key; it begins a
+ * CHAIN SEGMENT unless that record has the same chainID.  Rows and segments are numbered in the order of the text.  A chain ID
+ * that comes back after another therefore begins a new segment.  A row's atoms are those of the coordinate records from its
+ * first up to the next row's first, the next ENDMDL or the end of the file: the FIRST record of a slot gives the slot's
+ * position and b-factor, a later one of the same slot (an alternate location, a duplicate) is dropped and counted.
+ * MALFORMED.  kind FD_PDB_READ_SHORT: a coordinate record of fewer than 54 columns; FD_PDB_READ_COORD: x, y or z is blank or
+ * not a number as above (an exponent, two signs, a letter); FD_PDB_READ_NUMBER: occupancy or tempFactor is neither blank nor
+ * a number; FD_PDB_READ_RESSEQ: resSeq is not an integer.  A record's word is 8 (line number) + its smallest kind.
+ *
+ * Three launches; a thread owns FD_PDB_READ_WINDOW bytes, a block a chunk of FD_PDB_READ_CHUNK, nchunks = ceil(n / chunk); a line
+ * belongs to the window of its first byte.  All [k,nchunks] arrays are int64, row after row.
+ * fd_pdb_read_summary(..): summary [4,nchunks] = per chunk the lines that start in it, the ENDMDL lines among them, the position
+ *   of the last ENDMDL line and of the last ATOM (hetatm: or HETATM) line among them (-1: none).
+ * fd_pdb_read_count(..): carry [4,nchunks] = the same four of ALL chunks in front of each chunk (exclusive sums, running maxima,
+ *   -1 where there is none).  counts [3,nchunks] = residue rows and chain segments that begin in the chunk, and the smallest
+ *   word of a malformed record in it (FD_PDB_STATUS_OK: none).  file_first [2,F] int64 = per file that holds a byte the number
+ *   of its first line, and the ENDMDL lines in front of it (other entries are left alone).
+ * fd_pdb_read_fill(..): bases [2,nchunks] = exclusive sums of counts' first two rows; file_first as written above; T and C
+ *   their totals.  Writes, for row r: aatype [T] int64 and residue_index [T] int64 (resName and resSeq of the row's first
+ *   record), row_dropped [T] int32, and for every slot a record fills atom_positions [T,37,3] fp32, atom_mask [T,37] uint8 = 1
+ *   and b_factors [T,37] fp32 -- other entries are left alone (the caller zeroes them); for segment c: chain_first [C] int64
+ *   (its first row), chain_file, chain_model, chain_id [C] int32 (the chainID's character code).  Rows >= T and segments >= C
+ *   are not written.  Meant for text whose status is OK; a malformed field otherwise reads as 0.
+ * The scans are ordered and the first record of a slot wins whatever runs first: no atomics, two runs give the same bytes.
+ * Refused before any launch: n < 1, n > FD_PDB_READ_MAX_BYTES, F < 1, a null or misaligned operand. */
+#define FD_PDB_READ_WINDOW 16
+#define FD_PDB_READ_CHUNK 4096
+#define FD_PDB_READ_MAX_BYTES (1L << 40)
+#define FD_PDB_READ_SHORT 1
+#define FD_PDB_READ_COORD 2
+#define FD_PDB_READ_NUMBER 3
+#define FD_PDB_READ_RESSEQ 4
+int fd_pdb_read_summary(const unsigned char* text, long n, const long* file_offsets, int F, int hetatm, long* summary, void* stream);
+int fd_pdb_read_count(const unsigned char* text, long n, const long* file_offsets, int F, int hetatm, int model_all,
+                      const long* carry, long* counts, long* file_first, void* stream);
+int fd_pdb_read_fill(const unsigned char* text, long n, const long* file_offsets, int F, int hetatm, int model_all, const long* carry,
+                     const long* bases, const long* file_first, long T, long C, float* atom_positions, unsigned char* atom_mask,
+                     float* b_factors, long* aatype, long* residue_index, int* row_dropped, long* chain_first, int* chain_file,
+                     int* chain_model, int* chain_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

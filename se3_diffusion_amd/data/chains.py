@@ -20,7 +20,10 @@ the keys of the reference's DataLoader (those of ``train_step.synthetic_batch``)
 
 Out of scope: entries of several chains and chain_idx; aatype, side-chain torsions and the atom14 arrays; the evaluation branch of
 the dataset (t = 1, sample_ref(impute=...)); motif masks (PdbDataset._create_diffused_masks, which its own __getitem__ never
-calls: fixed_mask is zero); reading pickles, mmCIF or PDB files -- ``add`` takes arrays.
+calls: fixed_mask is zero); reading pickles or mmCIF -- ``add`` takes arrays.  PDB files come in through ``pdb.parse_pdb``, which
+reads them on the device, and ``add_parsed``, which takes its chain segments where they lie:
+
+    store.add_parsed(pdb.parse_pdb(my_pdb_paths))
 
 Three deliberate differences from the reference (include/fd_hip.h): res_mask needs N, CA and C, not CA alone; the frame of an
 absent residue and of a padding row is the identity at the origin behind res_mask = 0; quaternions have w >= 0.
@@ -44,6 +47,7 @@ class ChainStore:
     def __init__(self, device):
         self.device = torch.device(device)
         self._pending = []
+        self._parsed = []                            # (atoms, atom_mask, res_index on the device, host lengths) per add_parsed call
         self._frozen = False
         self.windows = None
 
@@ -54,6 +58,8 @@ class ChainStore:
         [L,4,3] = N, CA, C, O, atom_mask [L,4] and residue_index [L] (None: 0 .. L-1)."""
         if self._frozen:
             raise RuntimeError("ChainStore.add after freeze()")
+        if self._parsed:
+            raise RuntimeError("ChainStore.add after add_parsed(): the chains of add come first in the store")
         if chain is not None:
             if "atom_positions" in chain:
                 pos, msk = np.asarray(chain["atom_positions"]), np.asarray(chain["atom_mask"])
@@ -76,6 +82,30 @@ class ChainStore:
         self._pending.append((atoms, (atom_mask != 0).astype(np.uint8), residue_index.astype(np.int32)))
         return len(self._pending) - 1
 
+    def add_parsed(self, parsed, chains=None) -> list:
+        """The chain segments `chains` (indices into `parsed`, a pdb.ParsedPdb on this store's device; None: all of them) as
+        chains of the store; returns their ids.  The backbone columns 0, 1, 2, 4 of atom_positions and atom_mask and the residue
+        numbers are taken from the device arrays as they lie: nothing but the segment table (ParsedPdb.host_tables, read once)
+        comes to the host.  freeze() puts these chains behind those of add(), which therefore cannot be called any more."""
+        if self._frozen:
+            raise RuntimeError("ChainStore.add_parsed after freeze()")
+        if parsed.aatype.device.type != self.device.type:
+            raise ValueError(f"parsed lies on {parsed.aatype.device}, the store on {self.device}")
+        off = parsed.host_tables()[0]
+        cols = list(_BACKBONE37)
+        chosen = np.arange(len(parsed)) if chains is None else np.asarray(chains, dtype=np.int64).reshape(-1)
+        if len(chosen) and (chosen.min() < 0 or chosen.max() >= len(parsed)):
+            raise ValueError(f"chain segments must lie in [0, {len(parsed)}), got {chosen.min()} .. {chosen.max()}")
+        first = len(self._pending) + sum(len(p[3]) for p in self._parsed)
+        if chains is None:
+            rows = slice(0, parsed.num_residues)
+        else:
+            rows = torch.from_numpy(np.concatenate([np.arange(off[c], off[c + 1]) for c in chosen] + [np.zeros(0, np.int64)])
+                                    ).to(parsed.aatype.device)
+        self._parsed.append((parsed.atom_positions[rows][:, cols].contiguous(), parsed.atom_mask[rows][:, cols].contiguous(),
+                             parsed.residue_index[rows].to(torch.int32), (off[chosen + 1] - off[chosen]).astype(np.int64)))
+        return list(range(first, first + len(chosen)))
+
     def freeze(self):
         """Pack, upload, run fd_chain_windows and copy its [C,3] table to the host: the one synchronisation of the store."""
         if self._frozen:
@@ -87,8 +117,15 @@ class ChainStore:
         self.atoms = torch.from_numpy(np.ascontiguousarray(cat(0, (0, 4, 3), np.float32))).to(dev)
         self.atom_mask = torch.from_numpy(np.ascontiguousarray(cat(1, (0, 4), np.uint8))).to(dev)
         self.res_index = torch.from_numpy(np.ascontiguousarray(cat(2, (0,), np.int32))).to(dev)
+        if self._parsed:                             # the chains of add_parsed, already on the device, behind those of add
+            lens = np.concatenate([lens] + [p[3] for p in self._parsed])
+            C = len(lens)
+            self.atoms = torch.cat([self.atoms] + [p[0] for p in self._parsed])
+            self.atom_mask = torch.cat([self.atom_mask] + [p[1] for p in self._parsed])
+            self.res_index = torch.cat([self.res_index] + [p[2] for p in self._parsed])
         self.offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev)
         self._pending = None
+        self._parsed = None
         window = torch.empty((C, 3), dtype=torch.int32, device=dev)
         hip.get_lib().call("fd_chain_windows", self.atoms, self.atom_mask, self.offsets, C, window)
         self._window = window
@@ -97,7 +134,9 @@ class ChainStore:
         return self
 
     def __len__(self):
-        return len(self._pending) if not self._frozen else self.windows.shape[0]
+        if self._frozen:
+            return self.windows.shape[0]
+        return len(self._pending) + sum(len(p[3]) for p in self._parsed)
 
     @property
     def lengths(self):

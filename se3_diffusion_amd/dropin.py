@@ -23,6 +23,10 @@ signature and return value on the device-resident, hipGraph-replayed sampler:
 Writing: `install(..., device_pdb=True)` (shell: `--device-pdb`, next to `--device-inference` in either order) binds
 analysis.utils.write_prot_to_pdb -- one f-string per atom on the host -- to se3_diffusion_amd.pdb.write_prot_to_pdb, which formats the
 same bytes on the device.  Sampler.save_traj and Experiment.eval_fn reach it through `au.write_prot_to_pdb`.
+
+Reading: `install(..., device_pdb_read=True)` (shell: `--device-pdb-read`) binds data.utils.parse_pdb_feats -- Biopython's parser, an
+object per atom -- to se3_diffusion_amd.pdb.parse_pdb_feats, which reads the file on the device and returns the same dict.  The
+self-consistency loop of experiments/inference_se3_diffusion.py reaches it through `du.parse_pdb_feats`.
 """
 from __future__ import annotations
 
@@ -42,7 +46,7 @@ _RIGID = {"openfold.utils.rigid_utils": "se3_diffusion_amd.openfold.utils.rigid_
 
 
 def install(reference_root: str | None = None, replace_rigid_utils: bool = False, patch_all_atom: bool = True,
-            device_inference: bool = False, device_pdb: bool = False):
+            device_inference: bool = False, device_pdb: bool = False, device_pdb_read: bool = False):
     """Bind the reference's hot-path module paths to the HIP implementations.  Idempotent.
 
     replace_rigid_utils: also bind openfold.utils.rigid_utils to the eigh-free Rigid/Rotation of this
@@ -53,7 +57,10 @@ def install(reference_root: str | None = None, replace_rigid_utils: bool = False
     Experiment.inference_fn to inference.inference_fn.  Off by default: the reference's own loop stays.
 
     device_pdb: set analysis.utils.write_prot_to_pdb to pdb.write_prot_to_pdb (the same signature, file names and bytes), after
-    the bindings above.  Off by default: the reference's own writer stays."""
+    the bindings above.  Off by default: the reference's own writer stays.
+
+    device_pdb_read: set data.utils.parse_pdb_feats to pdb.parse_pdb_feats (the same signature and dict).  Off by default: the
+    reference's own reader stays."""
     if reference_root is not None:
         reference_root = os.path.abspath(reference_root)
         if not os.path.isdir(os.path.join(reference_root, "experiments")):
@@ -85,19 +92,23 @@ def install(reference_root: str | None = None, replace_rigid_utils: bool = False
     if device_pdb:
         from . import pdb
         importlib.import_module("analysis.utils").write_prot_to_pdb = pdb.write_prot_to_pdb
+    if device_pdb_read:
+        from . import pdb
+        importlib.import_module("data.utils").parse_pdb_feats = pdb.parse_pdb_feats
     return sorted(table)
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    flags = {"--device-inference": False, "--device-pdb": False}
+    flags = {"--device-inference": False, "--device-pdb": False, "--device-pdb-read": False}
     while argv and argv[0] in flags:
         flags[argv.pop(0)] = True
     if len(argv) < 2:
-        raise SystemExit("usage: python -m se3_diffusion_amd.dropin [--device-inference] [--device-pdb] <reference_root> <script.py> "
-                         "[args...]")
+        raise SystemExit("usage: python -m se3_diffusion_amd.dropin [--device-inference] [--device-pdb] [--device-pdb-read] "
+                         "<reference_root> <script.py> [args...]")
     root, script = argv[0], argv[1]
-    install(root, device_inference=flags["--device-inference"], device_pdb=flags["--device-pdb"])
+    install(root, device_inference=flags["--device-inference"], device_pdb=flags["--device-pdb"],
+            device_pdb_read=flags["--device-pdb-read"])
     sys.argv = [script] + argv[2:]
     os.chdir(root)
     runpy.run_path(os.path.join(root, script) if not os.path.isabs(script) else script, run_name="__main__")

@@ -300,6 +300,9 @@ _SIGS = {
     "fd_mpnn_decode": "pp" + "ilii" + "pppp" + "pppppp" + "fi" + "pppp" + "s",
     "fd_pdb_count": "plpp" + "ii" + "pp" + "s",
     "fd_pdb_format": "plppp" + "iil" + "pl" + "s",
+    "fd_pdb_read_summary": "plpi" + "i" + "p" + "s",
+    "fd_pdb_read_count": "plpi" + "ii" + "ppp" + "s",
+    "fd_pdb_read_fill": "plpi" + "ii" + "ppp" + "ll" + "pppppp" + "pppp" + "s",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

@@ -15,6 +15,17 @@ reference prints over-wide lines there.
 Inputs are taken as float32: a float64 array is ROUNDED to float32 first, so a float64 coordinate within half a float32 ulp of a
 %.3f tie may print one unit in the last place away from the reference's line for the float64 value.  The sampler's arrays are
 float32.
+
+Reading is the inverse (csrc/fd_pdb_read.hip): any number of files in one buffer, lines found, records classified by their
+columns, residues numbered by an ordered scan and atoms placed, on the device.
+
+    parsed = pdb.parse_pdb(paths_or_bytes_or_device_text)      # ParsedPdb: atom37 arrays packed over all chain segments
+    pos, mask = parsed.ca_padded()                             # what metrics.novelty / tm_align_matrix / aligned_rmsd take
+    frames = pdb.parse_pdb("bb_traj_1.pdb", model="all").models()
+    feats = pdb.parse_pdb_feats(name, path)                    # the reference's du.parse_pdb_feats, the same dict
+
+Reading back what format_pdb wrote gives float32(rint(x 1000) / 1000).  Not read: mmCIF, SEQRES and the other header records;
+of alternate locations the first is kept, not the one of the highest occupancy (parse_pdb's note).
 """
 from __future__ import annotations
 
@@ -163,3 +174,261 @@ def save_traj(out, b, output_dir, diffuse_mask=None):
         "traj_path": write_prot_to_pdb(prot, os.path.join(output_dir, "bb_traj"), b_factors=b_factors),
         "x0_traj_path": write_prot_to_pdb(x0, os.path.join(output_dir, "x0_traj"), b_factors=b_factors),
     }
+
+
+# ---- reading ---------------------------------------------------------------------------------------------------------------------
+READ_CHUNK = 4096                           # FD_PDB_READ_CHUNK
+READ_KINDS = {1: "a coordinate record shorter than 54 columns",
+              2: "a coordinate field that is empty or not a plain decimal number",
+              3: "an occupancy or b-factor field that is not a plain decimal number",
+              4: "a residue number that is not an integer"}
+_CA = 1                                     # atom37 slot of CA
+
+
+class ParsedPdb:
+    """What parse_pdb read, packed over all chain segments, on the device: atom_positions [T,37,3] fp32, atom_mask [T,37] uint8,
+    aatype [T] int64 (20: not one of the twenty), residue_index [T] int64 (resSeq as written), b_factors [T,37] fp32;
+    chain_offsets [C+1] int64 (segment c is rows chain_offsets[c] .. chain_offsets[c+1]), chain_file, chain_model (from 0, the
+    ENDMDL records in front of the segment in its file) and chain_id (a character code) [C] int32; n_dropped [F] int64, the
+    records per input file that lost their slot to an earlier one; n_files = F."""
+
+    def __init__(self, atom_positions, atom_mask, aatype, residue_index, b_factors, chain_offsets, chain_file, chain_model, chain_id,
+                 n_dropped, n_files):
+        self.atom_positions, self.atom_mask, self.aatype, self.residue_index, self.b_factors = \
+            atom_positions, atom_mask, aatype, residue_index, b_factors
+        self.chain_offsets, self.chain_file, self.chain_model, self.chain_id = chain_offsets, chain_file, chain_model, chain_id
+        self.n_dropped, self.n_files = n_dropped, n_files
+        self.n_lines = 0                        # lines of the whole input (set by parse_pdb)
+        self._host = None
+
+    def __len__(self):
+        return int(self.chain_file.numel())
+
+    @property
+    def num_residues(self):
+        return int(self.aatype.numel())
+
+    def host_tables(self):
+        """(chain_offsets, chain_file, chain_model, chain_id) as numpy; copied from the device on first use, then kept"""
+        if self._host is None:
+            self._host = tuple(t.cpu().numpy() for t in (self.chain_offsets, self.chain_file, self.chain_model, self.chain_id))
+        return self._host
+
+    def _rows(self, rows, chains):
+        """the segments `chains` (host indices), whose rows are `rows`: a slice (views) or an index tensor (copies)"""
+        off, cf, cm, ci = self.host_tables()
+        new_off = np.concatenate([[0], np.cumsum(off[chains + 1] - off[chains])]).astype(np.int64)
+        dev = self.aatype.device
+        pick = lambda t: t[rows]
+        idx = torch.from_numpy(chains).to(dev)
+        out = ParsedPdb(pick(self.atom_positions), pick(self.atom_mask), pick(self.aatype), pick(self.residue_index),
+                        pick(self.b_factors), torch.from_numpy(new_off).to(dev), self.chain_file[idx], self.chain_model[idx],
+                        self.chain_id[idx], self.n_dropped, self.n_files)
+        out._host = (new_off, cf[chains], cm[chains], ci[chains])
+        return out
+
+    def chain(self, i):
+        """Segment i alone: its rows as views of this object's tensors."""
+        off = self.host_tables()[0]
+        if not -len(self) <= i < len(self):
+            raise IndexError(f"chain {i} of {len(self)}")
+        i %= len(self)
+        return self._rows(slice(int(off[i]), int(off[i + 1])), np.array([i], np.int64))
+
+    def select(self, file=None, model=None, chain_id=None):
+        """The segments of input file `file`, model `model` (from 0) and chain `chain_id` (a character), None meaning any, in the
+        order of the text.  Views of this object's tensors when the chosen segments follow one another, copies otherwise."""
+        off, cf, cm, ci = self.host_tables()
+        keep = np.ones(len(cf), bool)
+        if file is not None:
+            keep &= cf == file
+        if model is not None:
+            keep &= cm == model
+        if chain_id is not None:
+            keep &= ci == ord(chain_id)
+        chains = np.flatnonzero(keep).astype(np.int64)
+        if len(chains) == 0:
+            return self._rows(slice(0, 0), chains)
+        if chains[-1] - chains[0] + 1 == len(chains):
+            return self._rows(slice(int(off[chains[0]]), int(off[chains[-1] + 1])), chains)
+        rows = np.concatenate([np.arange(off[c], off[c + 1]) for c in chains])
+        return self._rows(torch.from_numpy(rows).to(self.aatype.device), chains)
+
+    def ca_padded(self):
+        """(pos [C,Lmax,3] fp32, mask [C,Lmax] fp32): the CA atoms of every segment, padded to the longest, mask 1 where a CA was
+        read -- the operands of metrics.novelty, tm_align_matrix and aligned_rmsd."""
+        off = self.host_tables()[0]
+        C, T = len(self), self.num_residues
+        dev = self.aatype.device
+        lens = off[1:] - off[:-1]
+        Lmax = int(lens.max()) if C else 0
+        pos = torch.zeros((C, Lmax, 3), dtype=torch.float32, device=dev)
+        mask = torch.zeros((C, Lmax), dtype=torch.float32, device=dev)
+        if T:
+            starts = self.chain_offsets[:-1]
+            seg = torch.repeat_interleave(torch.arange(C, device=dev), self.chain_offsets[1:] - starts, output_size=T)
+            at = torch.arange(T, device=dev) - starts[seg]
+            pos[seg, at] = self.atom_positions[:, _CA]
+            mask[seg, at] = self.atom_mask[:, _CA].to(torch.float32)
+        return pos, mask
+
+    def models(self):
+        """atom_positions as [M,L,37,3] when this object holds one input file whose M models each are one segment with the same
+        residues (aatype and residue_index); ValueError otherwise.  Reads bb_traj / x0_traj files back."""
+        off, cf, cm, _ = self.host_tables()
+        M = len(cf)
+        if M == 0 or len(set(cf.tolist())) != 1 or sorted(cm.tolist()) != sorted(set(cm.tolist())):
+            raise ValueError("models() needs the segments of one file, one per model")
+        lens = off[1:] - off[:-1]
+        if len(set(lens.tolist())) != 1:
+            raise ValueError(f"the models differ in their number of residues: {sorted(set(lens.tolist()))}")
+        L = int(lens[0])
+        aa, ri = self.aatype.reshape(M, L), self.residue_index.reshape(M, L)
+        if not bool(((aa == aa[:1]).all() & (ri == ri[:1]).all()).item()):
+            raise ValueError("the models differ in their residues")
+        return self.atom_positions.reshape(M, L, 37, 3)
+
+
+def _gather_text(inputs, lib):
+    """(text uint8 on the device, 16-byte aligned; host int64 offsets [F+1]; names): host pieces are joined and uploaded in one copy"""
+    items = inputs if isinstance(inputs, (list, tuple)) else [inputs]
+    pieces, names = [], []
+    for k, it in enumerate(items):
+        if isinstance(it, torch.Tensor):
+            if it.dtype != torch.uint8 or it.dim() != 1:
+                raise ValueError(f"input {k}: a tensor must be uint8 [n], got {it.dtype} {tuple(it.shape)}")
+            pieces.append(it)
+            names.append(f"input {k}")
+        elif isinstance(it, (bytes, bytearray, memoryview)):
+            pieces.append(np.frombuffer(it, np.uint8))
+            names.append(f"input {k}")
+        elif isinstance(it, (str, os.PathLike)):
+            pieces.append(np.fromfile(os.fspath(it), np.uint8))
+            names.append(os.fspath(it))
+        else:
+            raise TypeError(f"input {k}: expected bytes, a uint8 tensor or a path, got {type(it).__name__}")
+    offsets = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in pieces])]).astype(np.int64)
+    on_dev = [p for p in pieces if isinstance(p, torch.Tensor) and (p.is_cuda or not lib.is_device)]
+    dev = on_dev[0].device if on_dev else _device_of(None, lib)
+    if len(pieces) == 1 and isinstance(pieces[0], torch.Tensor):
+        text = pieces[0].to(dev).contiguous()
+    elif not any(isinstance(p, torch.Tensor) for p in pieces):
+        text = torch.from_numpy(np.concatenate(pieces) if pieces else np.zeros(0, np.uint8)).to(dev)
+    else:
+        # host pieces go up in one copy, then everything is put in order on the device
+        host = [p for p in pieces if not isinstance(p, torch.Tensor)]
+        up = torch.from_numpy(np.concatenate(host)).to(dev) if host else None
+        parts, at = [], 0
+        for p in pieces:
+            if isinstance(p, torch.Tensor):
+                parts.append(p.to(dev))
+            else:
+                parts.append(up[at:at + p.shape[0]])
+                at += p.shape[0]
+        text = torch.cat(parts)
+    if text.data_ptr() % 16:
+        text = text.clone()
+    return text, offsets, names
+
+
+def parse_pdb(text_or_paths, hetatm=False, model="first"):
+    """Read PDB files into atom37 arrays on the device (csrc/fd_pdb_read.hip; include/fd_hip.h is the specification).
+
+    text_or_paths: bytes, a uint8 tensor already on the device (format_pdb's result), a path, or a list of these -- each entry is
+    one file; host entries are joined and uploaded in one copy.  hetatm=False: HETATM records are skipped like any other
+    line, so waters and ligands never become rows (the reference's process_chain turns HOH into an UNK residue).  model="first":
+    only the records in front of the first ENDMDL of each file; "all": every model, each a segment of its own.
+
+    Returns a ParsedPdb.  Three launches and a few scans; ONE read-back (the numbers of rows, segments and lines, and the status).
+    A malformed coordinate record (READ_KINDS) raises ValueError naming the file, the line in that file and the kind, before
+    anything is returned; the smallest line wins.  A file without a coordinate record gives no row.
+
+    Three differences from Biopython's object model, which the reference reads through: HETATM records (above); of several records
+    for one atom of a residue (alternate locations, duplicates) the FIRST is kept and the others counted in n_dropped, where
+    Biopython keeps the alternate location of the highest occupancy; a chain ID that comes back after another chain begins a
+    new segment, where Biopython merges the two.  mmCIF, SEQRES and the other header records are not read."""
+    if model not in ("first", "all"):
+        raise ValueError(f"model={model!r}: expected 'first' or 'all'")
+    lib = hip.get_lib()
+    text, offsets, names = _gather_text(text_or_paths, lib)
+    dev, n, F = text.device, int(text.numel()), len(offsets) - 1
+    i64 = dict(dtype=torch.int64, device=dev)
+    empty = lambda T, C: ParsedPdb(
+        torch.zeros((T, 37, 3), dtype=torch.float32, device=dev), torch.zeros((T, 37), dtype=torch.uint8, device=dev),
+        torch.empty(T, **i64), torch.empty(T, **i64), torch.zeros((T, 37), dtype=torch.float32, device=dev), torch.zeros(C + 1, **i64),
+        torch.empty(C, dtype=torch.int32, device=dev), torch.empty(C, dtype=torch.int32, device=dev),
+        torch.empty(C, dtype=torch.int32, device=dev), torch.zeros(F, **i64), F)
+    if n == 0:
+        return empty(0, 0)
+    off = torch.from_numpy(offsets).to(dev)
+    nchunks = -(-n // READ_CHUNK)
+    het, every = int(bool(hetatm)), int(model == "all")
+    summary = torch.empty((4, nchunks), **i64)
+    lib.call("fd_pdb_read_summary", text, n, off, F, het, summary)
+    carry = torch.empty((4, nchunks), **i64)
+    carry[:2] = torch.cumsum(summary[:2], 1) - summary[:2]
+    carry[2:, 0] = -1
+    carry[2:, 1:] = torch.cummax(summary[2:], 1).values[:, :-1]
+    counts = torch.empty((3, nchunks), **i64)
+    file_first = torch.zeros((2, F), **i64)
+    lib.call("fd_pdb_read_count", text, n, off, F, het, every, carry, counts, file_first)
+    ends = torch.cumsum(counts[:2], 1)
+    T, C, lines, word = (int(v) for v in torch.stack([ends[0, -1], ends[1, -1], summary[0].sum(), counts[2].min()]).cpu())
+    if word != STATUS_OK:
+        line, kind = divmod(word, 8)
+        first = file_first[0].cpu().numpy()
+        f = max(g for g in range(F) if offsets[g + 1] > offsets[g] and first[g] <= line)
+        raise ValueError(f"cannot be read as PDB text: {READ_KINDS.get(kind, kind)} in file {f} ({names[f]}), line {line - first[f] + 1}")
+    out = empty(T, C)
+    out.n_lines = lines
+    if T:
+        bases = (ends - counts[:2]).contiguous()
+        dropped = torch.empty(T, dtype=torch.int32, device=dev)
+        lib.call("fd_pdb_read_fill", text, n, off, F, het, every, carry, bases, file_first, T, C, out.atom_positions, out.atom_mask,
+                 out.b_factors, out.aatype, out.residue_index, dropped, out.chain_offsets, out.chain_file, out.chain_model,
+                 out.chain_id)
+        out.chain_offsets[C] = T
+        seg = torch.repeat_interleave(torch.arange(C, device=dev), out.chain_offsets[1:] - out.chain_offsets[:-1], output_size=T)
+        out.n_dropped.index_add_(0, out.chain_file[seg].to(torch.int64), dropped.to(torch.int64))
+    return out
+
+
+def parse_pdb_feats(pdb_name, pdb_path, scale_factor=1., chain_id='A'):
+    """The reference's data.utils.parse_pdb_feats with the file read on the device: the same signature and the same dict of numpy
+    arrays -- atom_positions [L,37,3], atom_mask [L,37], b_factors [L,37] (float64), aatype, residue_index [L] (int64), bb_mask [L],
+    bb_positions [L,3] -- for chain_id a string; a dict of those by chain for a list, or for None (every chain of the file).
+    The first model is read, without HETATM records (parse_pdb's note).  Segments that share a chain ID are joined in file order,
+    as Biopython's chains are.  Centring and scaling are parse_chain_feats' arithmetic in float64 numpy on the arrays read
+    back.  b-factors are widened through their shortest decimal: a field of six columns survives float32 unchanged, so this is
+    float(field), what Biopython stores."""
+    del pdb_name
+    parsed = parse_pdb(pdb_path, hetatm=False, model="first")
+    _, _, _, ci = parsed.host_tables()
+    ids = [chr(c) for c in ci]
+    host = {}
+
+    def _process_chain_id(x):
+        if x not in ids:
+            raise KeyError(x)
+        if not host:
+            host.update(pos=parsed.atom_positions.cpu().numpy(), mask=parsed.atom_mask.cpu().numpy(),
+                        aa=parsed.aatype.cpu().numpy(), ri=parsed.residue_index.cpu().numpy(), b=parsed.b_factors.cpu().numpy())
+        off = parsed.host_tables()[0]
+        rows = np.concatenate([np.arange(off[c], off[c + 1]) for c, i in enumerate(ids) if i == x])
+        feats = {"atom_positions": host["pos"][rows].astype(np.float64), "aatype": host["aa"][rows].astype(np.int64),
+                 "atom_mask": host["mask"][rows].astype(np.float64), "residue_index": host["ri"][rows].astype(np.int64),
+                 "b_factors": host["b"][rows].astype(str).astype(np.float64)}
+        feats["bb_mask"] = feats["atom_mask"][:, _CA]
+        bb_center = np.sum(feats["atom_positions"][:, _CA], axis=0) / (np.sum(feats["bb_mask"]) + 1e-5)
+        centered = feats["atom_positions"] - bb_center[None, None, :]
+        feats["atom_positions"] = (centered / scale_factor) * feats["atom_mask"][..., None]
+        feats["bb_positions"] = feats["atom_positions"][:, _CA]
+        return feats
+
+    if isinstance(chain_id, str):
+        return _process_chain_id(chain_id)
+    if isinstance(chain_id, list):
+        return {x: _process_chain_id(x) for x in chain_id}
+    if chain_id is None:
+        return {x: _process_chain_id(x) for x in dict.fromkeys(ids)}
+    raise ValueError(f'Unrecognized chain list {chain_id}')

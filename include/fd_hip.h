@@ -1341,6 +1341,107 @@ int fd_pdb_read_fill(const unsigned char* text, long n, const long* file_offsets
                      float* b_factors, long* aatype, long* residue_index, int* row_dropped, long* chain_first, int* chain_file,
                      int* chain_model, int* chain_id, void* stream);
 
+/* ---- reading mmCIF text (se3_diffusion_amd/csrc/fd_cif_read.hip) ----
+ * The same arrays from the _atom_site loop of F mmCIF files that lie end to end in text, given as in the section above.
+ *
+ * LINES are those of the section above: a line starts at the first byte of a file and behind every '\n', a '\r' directly in
+ * front of its end is not part of it, lines are numbered from 0 through all files.  There is no column limit.  Blanks and tabs
+ * separate tokens.
+ * TEXT FIELDS.  A line whose first byte is ';' is a ';'-line.  A line lies inside a text field when the ';'-lines of its file in
+ * front of it are odd in number.  Such lines and the ';'-lines themselves are not syntax, whatever they look like: they count
+ * as OTHER lines below.
+ * CLASSES.  Every other line is classified by its first token behind leading blanks; keywords and tag names compare without
+ * regard to ASCII case.  BLANK: no token.  LOOP: the token is "loop_" (what follows it on the line is not read).  TAG: the token
+ * begins with "_atom_site." (the dot included, so _atom_site_anisotrop. is none) and nothing but blanks or a '#' comment follows
+ * it on the line.  OTHER: any other token that begins with '_' (an _atom_site. tag with a value behind it, the key-value form,
+ * among them), with "data_" or with '#'.  VALUE: anything else.
+ * THE LOOP.  A LOOP line is a HEAD when the next line of its file that is not BLANK is a TAG line.  The head's COLUMNS are the
+ * TAG lines behind it up to the first line that is neither TAG nor BLANK, numbered from 0; their number is the loop's width.  A
+ * VALUE line is a ROW when, of the lines of its file in front of it, the last LOOP line is a head, a TAG line lies behind that
+ * head, and no OTHER line lies behind that head.  So the rows end at the first line that is neither VALUE nor BLANK; one row per
+ * line; a file without a head has no row.  A second head in one file is malformed.
+ * TOKENS of a row: a run of bytes that are neither blank nor tab; or, where that run begins with ' or ", the bytes behind that
+ * quote up to the next occurrence of the same quote that is followed by a blank, a tab or the line's end ("O5'" is the three
+ * bytes O5').  A token that begins with '#' ends the row.  A row has as many tokens as the loop has columns and at most
+ * FD_CIF_MAX_LINE bytes; a longer line is not tokenised.
+ * COLUMNS that are read, by the tag's name behind "_atom_site." (of two columns of one name the later one):
+ *   group_PDB            "HETATM" makes a HETATM record, anything else ATOM; no such column: every row is ATOM
+ *   label_atom_id        the atom name: one of the 37 atom37 names gives the slot, any other name none
+ *   label_alt_id         must be there; it is not looked at (the first record of a slot wins, as above)
+ *   label_comp_id        -> aatype as above
+ *   auth_asym_id         the chain ID: 1 to 4 bytes, packed into an int32 with the first byte lowest, so that a one-letter ID is
+ *                        its character code; "." and "?" read as a blank (32).  label_asym_id where there is no such column,
+ *                        and always with ids_label != 0
+ *   auth_seq_id          the residue number, a signed integer; label_seq_id where there is no such column, and always with
+ *                        ids_label != 0
+ *   pdbx_PDB_ins_code    the token's first byte; ".", "?" or no such column: a blank
+ *   Cartn_x, Cartn_y, Cartn_z
+ *   occupancy            ".", "?" or no such column: 1 (checked, not stored)
+ *   B_iso_or_equiv       ".", "?" or no such column: 0
+ *   pdbx_PDB_model_num   an integer; no such column: 1
+ * Every other column is tokenised and skipped.  The columns may stand in any order; the order is taken per file.
+ * NUMBERS.  A token that is an optional sign and digits with at most one '.' among them, at least one and at most 15 digits, no
+ * exponent; the value as in the section above.
+ * RECORDS.  The COORDINATE RECORDS are the rows that are not HETATM, and all rows iff hetatm != 0; a row that cannot be tokenised
+ * counts as one.  With model_all == 0 only those whose model number is that of the file's first coordinate record are SELECTED.
+ * RESIDUES, CHAIN SEGMENTS, SLOTS: as in the section above with the key (chain ID, residue number, insertion code, HETATM or
+ * not): a selected record begins a residue row unless the coordinate record before it lies in the same file and has the same
+ * model number and key; it begins a chain segment unless that record has the same chain ID and model number.  A row's atoms are
+ * those of the coordinate records from its first up to the first with another key or model number, or the end of the loop's
+ * rows.  A segment's model is its model number minus that of its file's first coordinate record.
+ * MALFORMED.  The word is 8 (line number) + kind.  FD_CIF_READ_COLUMNS, at a head's LOOP line: one of label_atom_id,
+ * label_alt_id, label_comp_id, Cartn_x, Cartn_y, Cartn_z, the chain ID's or the residue number's column is missing; more than
+ * FD_CIF_MAX_COLS columns; a second head in the file.  Of a coordinate record, the smallest of: FD_CIF_READ_TOKENS (a wrong
+ * number of tokens, an unclosed quote, a line longer than FD_CIF_MAX_LINE; nothing else is checked then); and, unless the model
+ * number is an integer and the record is not selected: FD_CIF_READ_COORD, FD_CIF_READ_NUMBER, FD_CIF_READ_RESSEQ as in the
+ * section above, FD_CIF_READ_CHAIN (a chain ID of no or more than 4 bytes), FD_CIF_READ_MODEL (not an integer).
+ *
+ * Six launches with the windows and chunks of the section above.  What a line is depends on the text in front of it, so the
+ * values that the ordered scan carries are found in stages: each launch writes per chunk what the next needs, and the caller
+ * turns it into rows of carry [8,nchunks] int64 = for each chunk, of ALL chunks in front of it (-1 where there is none):
+ *   0 the lines; 1 the ';'-lines; 2 the ';'-lines in front of the last file start; 3 .. 6 the position of the last LOOP, TAG,
+ *   OTHER and head line; 7 the position of the last coordinate record.
+ * A launch reads the rows that the launches in front of it made complete; the others hold -1.
+ * fd_cif_read_lines(..): lines [3,nchunks] = per chunk the lines that start in it, the ';'-lines among them, and the ';'-lines of
+ *   the chunk in front of its last file start (-1: no file starts in it).  Carry rows 0 and 1 are exclusive sums; row 2 is the
+ *   running maximum over the chunks in front of (row 1 + lines' third row) where that row is not -1.
+ * fd_cif_read_marks(..): marks [4,nchunks] = the four positions among the chunk's lines or those in front (-1: none); carry
+ *   rows 3 .. 6 are running maxima over the chunks in front.
+ * fd_cif_read_header(..): table [F,FD_CIF_TABLE] int32 = per file with a head: for column k < FD_CIF_MAX_COLS the field it is
+ *   read as in the order of the list above (0 group_PDB .. 12 pdbx_PDB_model_num; -1: skipped), then the loop's width and the
+ *   model number of the file's first coordinate record; file_first [F] int64 = per file that holds a byte the number of its
+ *   first line; bad [nchunks] = the smallest word of a malformed head in the chunk (FD_PDB_STATUS_OK: none).  Other entries are
+ *   left alone.
+ * fd_cif_read_summary(..): last [nchunks] = the position of the last coordinate record among the chunk's lines or those in
+ *   front; carry row 7 is its running maximum over the chunks in front.
+ * fd_cif_read_count(..): counts [3,nchunks] as fd_pdb_read_count's.
+ * fd_cif_read_fill(..): bases, T, C and the outputs as fd_pdb_read_fill's; chain_id holds the packed chain ID.  Rows >= T and
+ *   segments >= C are not written, entries that no record fills are left alone.
+ * The scans are ordered and the first record of a slot wins whatever runs first: no atomics, two runs give the same bytes.
+ * Refused before any launch: what the section above refuses. */
+#define FD_CIF_MAX_COLS 64
+#define FD_CIF_MAX_LINE 1024
+#define FD_CIF_TABLE 66
+#define FD_CIF_READ_TOKENS 1
+#define FD_CIF_READ_COORD 2
+#define FD_CIF_READ_NUMBER 3
+#define FD_CIF_READ_RESSEQ 4
+#define FD_CIF_READ_COLUMNS 5
+#define FD_CIF_READ_CHAIN 6
+#define FD_CIF_READ_MODEL 7
+int fd_cif_read_lines(const unsigned char* text, long n, const long* file_offsets, int F, long* lines, void* stream);
+int fd_cif_read_marks(const unsigned char* text, long n, const long* file_offsets, int F, const long* carry, long* marks, void* stream);
+int fd_cif_read_header(const unsigned char* text, long n, const long* file_offsets, int F, int hetatm, int ids_label,
+                       const long* carry, int* table, long* file_first, long* bad, void* stream);
+int fd_cif_read_summary(const unsigned char* text, long n, const long* file_offsets, int F, int hetatm, const long* carry,
+                        const int* table, long* last, void* stream);
+int fd_cif_read_count(const unsigned char* text, long n, const long* file_offsets, int F, int hetatm, int model_all,
+                      const long* carry, const int* table, long* counts, void* stream);
+int fd_cif_read_fill(const unsigned char* text, long n, const long* file_offsets, int F, int hetatm, int model_all, const long* carry,
+                     const int* table, const long* bases, long T, long C, float* atom_positions, unsigned char* atom_mask,
+                     float* b_factors, long* aatype, long* residue_index, int* row_dropped, long* chain_first, int* chain_file,
+                     int* chain_model, int* chain_id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -303,6 +303,12 @@ _SIGS = {
     "fd_pdb_read_summary": "plpi" + "i" + "p" + "s",
     "fd_pdb_read_count": "plpi" + "ii" + "ppp" + "s",
     "fd_pdb_read_fill": "plpi" + "ii" + "ppp" + "ll" + "pppppp" + "pppp" + "s",
+    "fd_cif_read_lines": "plpi" + "p" + "s",
+    "fd_cif_read_marks": "plpi" + "pp" + "s",
+    "fd_cif_read_header": "plpi" + "ii" + "pppp" + "s",
+    "fd_cif_read_summary": "plpi" + "i" + "ppp" + "s",
+    "fd_cif_read_count": "plpi" + "ii" + "ppp" + "s",
+    "fd_cif_read_fill": "plpi" + "ii" + "ppp" + "ll" + "pppppp" + "pppp" + "s",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

@@ -24,8 +24,11 @@ columns, residues numbered by an ordered scan and atoms placed, on the device.
     frames = pdb.parse_pdb("bb_traj_1.pdb", model="all").models()
     feats = pdb.parse_pdb_feats(name, path)                    # the reference's du.parse_pdb_feats, the same dict
 
-Reading back what format_pdb wrote gives float32(rint(x 1000) / 1000).  Not read: mmCIF, SEQRES and the other header records;
-of alternate locations the first is kept, not the one of the highest occupancy (parse_pdb's note).
+    parsed = pdb.parse_mmcif(paths_or_bytes_or_device_text)    # the same object from the _atom_site loop of mmCIF files
+
+Reading back what format_pdb wrote gives float32(rint(x 1000) / 1000).  Not read: SEQRES and the other header records; of
+alternate locations the first is kept, not the one of the highest occupancy (parse_pdb's note).  mmCIF is read by parse_mmcif
+(csrc/fd_cif_read.hip): the _atom_site loop under the same rules, nothing else of the file.
 """
 from __future__ import annotations
 
@@ -189,7 +192,8 @@ class ParsedPdb:
     """What parse_pdb read, packed over all chain segments, on the device: atom_positions [T,37,3] fp32, atom_mask [T,37] uint8,
     aatype [T] int64 (20: not one of the twenty), residue_index [T] int64 (resSeq as written), b_factors [T,37] fp32;
     chain_offsets [C+1] int64 (segment c is rows chain_offsets[c] .. chain_offsets[c+1]), chain_file, chain_model (from 0, the
-    ENDMDL records in front of the segment in its file) and chain_id (a character code) [C] int32; n_dropped [F] int64, the
+    ENDMDL records in front of the segment in its file) and chain_id (a character code; from parse_mmcif up to four of them, the
+    first lowest: chain_names()) [C] int32; n_dropped [F] int64, the
     records per input file that lost their slot to an earlier one; n_files = F."""
 
     def __init__(self, atom_positions, atom_mask, aatype, residue_index, b_factors, chain_offsets, chain_file, chain_model, chain_id,
@@ -236,8 +240,8 @@ class ParsedPdb:
         return self._rows(slice(int(off[i]), int(off[i + 1])), np.array([i], np.int64))
 
     def select(self, file=None, model=None, chain_id=None):
-        """The segments of input file `file`, model `model` (from 0) and chain `chain_id` (a character), None meaning any, in the
-        order of the text.  Views of this object's tensors when the chosen segments follow one another, copies otherwise."""
+        """The segments of input file `file`, model `model` (from 0) and chain `chain_id` (a string of 1 to 4 characters), None
+        meaning any, in the order of the text.  Views of this object's tensors when the chosen segments follow one another, copies otherwise."""
         off, cf, cm, ci = self.host_tables()
         keep = np.ones(len(cf), bool)
         if file is not None:
@@ -245,7 +249,7 @@ class ParsedPdb:
         if model is not None:
             keep &= cm == model
         if chain_id is not None:
-            keep &= ci == ord(chain_id)
+            keep &= ci == _pack_chain(chain_id)
         chains = np.flatnonzero(keep).astype(np.int64)
         if len(chains) == 0:
             return self._rows(slice(0, 0), chains)
@@ -253,6 +257,10 @@ class ParsedPdb:
             return self._rows(slice(int(off[chains[0]]), int(off[chains[-1] + 1])), chains)
         rows = np.concatenate([np.arange(off[c], off[c + 1]) for c in chains])
         return self._rows(torch.from_numpy(rows).to(self.aatype.device), chains)
+
+    def chain_names(self):
+        """chain_id unpacked: per segment the chain ID as a string (parse_pdb: one character)"""
+        return [int(c).to_bytes(4, "little", signed=True).rstrip(b"\0").decode("latin-1") for c in self.host_tables()[3]]
 
     def ca_padded(self):
         """(pos [C,Lmax,3] fp32, mask [C,Lmax] fp32): the CA atoms of every segment, padded to the longest, mask 1 where a CA was
@@ -287,6 +295,14 @@ class ParsedPdb:
         if not bool(((aa == aa[:1]).all() & (ri == ri[:1]).all()).item()):
             raise ValueError("the models differ in their residues")
         return self.atom_positions.reshape(M, L, 37, 3)
+
+
+def _pack_chain(chain_id):
+    """a chain ID of 1 to 4 characters as chain_id holds it: the first character lowest"""
+    raw = chain_id.encode("latin-1")
+    if not 1 <= len(raw) <= 4:
+        raise ValueError(f"chain_id={chain_id!r}: expected 1 to 4 characters")
+    return int.from_bytes(raw.ljust(4, b"\0"), "little", signed=True)
 
 
 def _gather_text(inputs, lib):
@@ -331,6 +347,24 @@ def _gather_text(inputs, lib):
     return text, offsets, names
 
 
+def _empty_parsed(dev, F, T, C):
+    """a ParsedPdb of T rows in C segments from F files for a fill kernel to write into: zeros where no record may write"""
+    i64 = dict(dtype=torch.int64, device=dev)
+    return ParsedPdb(
+        torch.zeros((T, 37, 3), dtype=torch.float32, device=dev), torch.zeros((T, 37), dtype=torch.uint8, device=dev),
+        torch.empty(T, **i64), torch.empty(T, **i64), torch.zeros((T, 37), dtype=torch.float32, device=dev), torch.zeros(C + 1, **i64),
+        torch.empty(C, dtype=torch.int32, device=dev), torch.empty(C, dtype=torch.int32, device=dev),
+        torch.empty(C, dtype=torch.int32, device=dev), torch.zeros(F, **i64), F)
+
+
+def _close(out, dropped):
+    """behind a fill kernel: the last chain offset, and the dropped records of the rows summed per file"""
+    T, C, dev = out.num_residues, len(out), out.aatype.device
+    out.chain_offsets[C] = T
+    seg = torch.repeat_interleave(torch.arange(C, device=dev), out.chain_offsets[1:] - out.chain_offsets[:-1], output_size=T)
+    out.n_dropped.index_add_(0, out.chain_file[seg].to(torch.int64), dropped.to(torch.int64))
+
+
 def parse_pdb(text_or_paths, hetatm=False, model="first"):
     """Read PDB files into atom37 arrays on the device (csrc/fd_pdb_read.hip; include/fd_hip.h is the specification).
 
@@ -346,18 +380,14 @@ def parse_pdb(text_or_paths, hetatm=False, model="first"):
     Three differences from Biopython's object model, which the reference reads through: HETATM records (above); of several records
     for one atom of a residue (alternate locations, duplicates) the FIRST is kept and the others counted in n_dropped, where
     Biopython keeps the alternate location of the highest occupancy; a chain ID that comes back after another chain begins a
-    new segment, where Biopython merges the two.  mmCIF, SEQRES and the other header records are not read."""
+    new segment, where Biopython merges the two.  SEQRES and the other header records are not read; mmCIF is parse_mmcif's."""
     if model not in ("first", "all"):
         raise ValueError(f"model={model!r}: expected 'first' or 'all'")
     lib = hip.get_lib()
     text, offsets, names = _gather_text(text_or_paths, lib)
     dev, n, F = text.device, int(text.numel()), len(offsets) - 1
     i64 = dict(dtype=torch.int64, device=dev)
-    empty = lambda T, C: ParsedPdb(
-        torch.zeros((T, 37, 3), dtype=torch.float32, device=dev), torch.zeros((T, 37), dtype=torch.uint8, device=dev),
-        torch.empty(T, **i64), torch.empty(T, **i64), torch.zeros((T, 37), dtype=torch.float32, device=dev), torch.zeros(C + 1, **i64),
-        torch.empty(C, dtype=torch.int32, device=dev), torch.empty(C, dtype=torch.int32, device=dev),
-        torch.empty(C, dtype=torch.int32, device=dev), torch.zeros(F, **i64), F)
+    empty = lambda T, C: _empty_parsed(dev, F, T, C)
     if n == 0:
         return empty(0, 0)
     off = torch.from_numpy(offsets).to(dev)
@@ -387,9 +417,89 @@ def parse_pdb(text_or_paths, hetatm=False, model="first"):
         lib.call("fd_pdb_read_fill", text, n, off, F, het, every, carry, bases, file_first, T, C, out.atom_positions, out.atom_mask,
                  out.b_factors, out.aatype, out.residue_index, dropped, out.chain_offsets, out.chain_file, out.chain_model,
                  out.chain_id)
-        out.chain_offsets[C] = T
-        seg = torch.repeat_interleave(torch.arange(C, device=dev), out.chain_offsets[1:] - out.chain_offsets[:-1], output_size=T)
-        out.n_dropped.index_add_(0, out.chain_file[seg].to(torch.int64), dropped.to(torch.int64))
+        _close(out, dropped)
+    return out
+
+
+CIF_TABLE = 66                              # FD_CIF_TABLE
+CIF_KINDS = {1: "a row with a wrong number of tokens, an unclosed quote or more than 1024 bytes",
+             2: "a coordinate that is empty or not a plain decimal number",
+             3: "an occupancy or b-factor that is not a plain decimal number",
+             4: "a residue number that is not an integer",
+             5: "an atom_site loop without a needed column, with more than 64 columns, or a second one in the file",
+             6: "a chain ID of more than 4 characters",
+             7: "a model number that is not an integer"}
+
+
+def parse_mmcif(text_or_paths, hetatm=False, model="first", ids="auth"):
+    """Read the _atom_site loop of mmCIF files into atom37 arrays on the device (csrc/fd_cif_read.hip; include/fd_hip.h is the
+    specification).  The inputs, the result and the rules for residues, segments, slots and models are parse_pdb's, with the
+    pdbx_PDB_model_num column in place of ENDMDL records: model="first" keeps the rows that carry the model number of the file's
+    first coordinate record, and chain_model is a segment's model number minus that one.  All entries of one call are mmCIF.
+
+    The columns are found by their tags in any order, per file: group_PDB, label_atom_id, label_alt_id, label_comp_id,
+    auth_asym_id and auth_seq_id (ids="auth"; label_asym_id and label_seq_id where those are absent, and always with
+    ids="label"), pdbx_PDB_ins_code, Cartn_x / y / z, occupancy, B_iso_or_equiv, pdbx_PDB_model_num -- Biopython's choices.  A
+    chain ID has 1 to 4 characters and is packed into chain_id with the first lowest, so "A" is what parse_pdb gives;
+    chain_names() unpacks, select(chain_id="AA") picks.
+
+    Six launches and a few scans; ONE read-back.  A malformed loop head or coordinate record (CIF_KINDS) raises ValueError naming
+    the file, the line in that file and the kind, before anything is returned; the smallest line wins.  A file without an
+    atom_site loop, or with atom_site in key-value form, gives no row.
+
+    Not read: _entity_poly_seq and any SEQRES-like alignment; the header items the reference's metadata uses (resolution,
+    method, oligomeric state); rows that span lines and text fields inside the loop; several tags on one line; gzip (pass the
+    inflated bytes).  parse_pdb's three differences from Biopython's object model hold here too.  The reader is checked against
+    parse_pdb on the same structures and against a pure-Python tokeniser written from the header's rules (tests/test_mmcif_read.py),
+    NOT against Biopython's MMCIFParser, which does not exist where this project is built."""
+    if model not in ("first", "all"):
+        raise ValueError(f"model={model!r}: expected 'first' or 'all'")
+    if ids not in ("auth", "label"):
+        raise ValueError(f"ids={ids!r}: expected 'auth' or 'label'")
+    lib = hip.get_lib()
+    text, offsets, names = _gather_text(text_or_paths, lib)
+    dev, n, F = text.device, int(text.numel()), len(offsets) - 1
+    i64 = dict(dtype=torch.int64, device=dev)
+    if n == 0:
+        return _empty_parsed(dev, F, 0, 0)
+    off = torch.from_numpy(offsets).to(dev)
+    nchunks = -(-n // READ_CHUNK)
+    het, every = int(bool(hetatm)), int(model == "all")
+    before = lambda v: torch.cat([torch.full_like(v[:, :1], -1), torch.cummax(v, 1).values[:, :-1]], 1)   # of the chunks in front
+    carry = torch.full((8, nchunks), -1, **i64)
+    lines = torch.empty((3, nchunks), **i64)
+    lib.call("fd_cif_read_lines", text, n, off, F, lines)
+    carry[:2] = torch.cumsum(lines[:2], 1) - lines[:2]
+    carry[2:3] = before(torch.where(lines[2:3] >= 0, carry[1:2] + lines[2:3], lines[2:3]))
+    marks = torch.empty((4, nchunks), **i64)
+    lib.call("fd_cif_read_marks", text, n, off, F, carry, marks)
+    carry[3:7] = before(marks)
+    table = torch.zeros((F, CIF_TABLE), dtype=torch.int32, device=dev)
+    file_first = torch.zeros(F, **i64)
+    head_bad = torch.empty(nchunks, **i64)
+    lib.call("fd_cif_read_header", text, n, off, F, het, int(ids == "label"), carry, table, file_first, head_bad)
+    last = torch.empty((1, nchunks), **i64)
+    lib.call("fd_cif_read_summary", text, n, off, F, het, carry, table, last)
+    carry[7:8] = before(last)
+    counts = torch.empty((3, nchunks), **i64)
+    lib.call("fd_cif_read_count", text, n, off, F, het, every, carry, table, counts)
+    ends = torch.cumsum(counts[:2], 1)
+    T, C, n_lines, word = (int(v) for v in torch.stack([ends[0, -1], ends[1, -1], lines[0].sum(),
+                                                        torch.minimum(counts[2].min(), head_bad.min())]).cpu())
+    if word != STATUS_OK:
+        line, kind = divmod(word, 8)
+        first = file_first.cpu().numpy()
+        f = max(g for g in range(F) if offsets[g + 1] > offsets[g] and first[g] <= line)
+        raise ValueError(f"cannot be read as mmCIF text: {CIF_KINDS.get(kind, kind)} in file {f} ({names[f]}), line {line - first[f] + 1}")
+    out = _empty_parsed(dev, F, T, C)
+    out.n_lines = n_lines
+    if T:
+        bases = (ends - counts[:2]).contiguous()
+        dropped = torch.empty(T, dtype=torch.int32, device=dev)
+        lib.call("fd_cif_read_fill", text, n, off, F, het, every, carry, table, bases, T, C, out.atom_positions, out.atom_mask,
+                 out.b_factors, out.aatype, out.residue_index, dropped, out.chain_offsets, out.chain_file, out.chain_model,
+                 out.chain_id)
+        _close(out, dropped)
     return out
 
 

@@ -1442,6 +1442,59 @@ int fd_cif_read_fill(const unsigned char* text, long n, const long* file_offsets
                      float* b_factors, long* aatype, long* residue_index, int* row_dropped, long* chain_first, int* chain_file,
                      int* chain_model, int* chain_id, void* stream);
 
+/* ---- sequence alignment and clustering (se3_diffusion_amd/csrc/fd_seq.hip) ----
+ * Sequences are packed as the chain store packs chains: letters [T] uint8, values 0 .. 20 in the reference's restypes order
+ * (ARNDCQEGHILKMFPSTWYV, 20 = X), chain c being the rows offsets[c] .. offsets[c+1] - 1 (offsets [C+1] int64, 0 first, not
+ * decreasing).
+ *
+ * fd_seq_align(..): Gotoh's local alignment with affine gaps of every pair of the rectangle ids_a [Pa] x ids_b [Pb] (int32 chain
+ * ids, repeats allowed): for entry (ia, ib), x = chain ids_a[ia] of m residues and y = chain ids_b[ib] of n.  subst [21,21] int32
+ * is indexed [letter of x][letter of y] and need not be symmetric; a gap of k residues costs gap_open + k gap_extend.  The
+ * optimal path's statistics travel with its score, so no traceback is stored.  A cell state is the tuple (score, matches,
+ * columns, i0, j0), and THE RECURRENCE ON THESE TUPLES IS THE SPECIFICATION (i, j from 0; H outside the matrix is empty, E and F
+ * outside it are absent):
+ *   E(i,j), a gap that consumes y_j: E(i,j-1) with score - gap_extend, or H(i,j-1) with score - gap_open - gap_extend; the
+ *           extension where the two scores tie.  The chosen tuple keeps its matches and its start and gains one column.
+ *   F(i,j), a gap that consumes x_i: the same from (i-1,j).
+ *   D(i,j): H(i-1,j-1) with subst[x_i][y_j] added to the score, (x_i == y_j) to the matches and one column; from an empty cell
+ *           it starts at (i0, j0) = (i, j).
+ *   H(i,j): the best of D, E, F by score, D before E before F on equal scores; if that score is <= 0 the cell is EMPTY: score
+ *           0, no statistics.
+ *   The result is the H of the largest score; on equal scores that of the smallest i, then of the smallest j.
+ * out [Pa,Pb,FD_SEQ_SLOTS] int32 (16-byte aligned) = score, matches, columns, a_begin, a_end, b_begin, b_end, 0 with positions
+ * from 0, inclusive (a_begin = i0, a_end = i); a score of 0 (also m == 0 or n == 0) gives 0, 0, 0, -1, -1, -1, -1, 0.  Letter
+ * 20 equals itself like any other.  align(a, b) is not the transpose of align(b, a): the tie rules are not symmetric.  With
+ * upper_only != 0 the entries with ids_a[ia] >= ids_b[ib] are not computed and hold -1 in all slots.  Every element of out is
+ * written.  One wave per pair, the matrix in registers; integer arithmetic only, no atomics: two runs give the same words.
+ * Pa == 0 or Pb == 0 returns FD_OK without a launch.  What is refused depends on what the operands hold, so the call copies
+ * offsets, the ids, the table and the letters to the host first: it waits for the stream and cannot be captured into a graph.
+ * Refused before any launch (FD_ERR_ARG): a negative size, a null or misaligned operand, gap_open outside 0 .. FD_SEQ_MAX_GAP,
+ * gap_extend outside 1 .. FD_SEQ_MAX_GAP, a table entry outside -FD_SEQ_MAX_SCORE .. FD_SEQ_MAX_SCORE, offsets that do not start
+ * at 0 or decrease, an id outside [0, C), a named chain of more than FD_SEQ_MAX_L residues, a letter above 20.  The kernel
+ * clamps the letter it uses as a table index and the lengths it uses as loop bounds regardless.
+ * There is no published substitution matrix in the library: the caller passes the table (se3_diffusion_amd/seqs.py holds a
+ * BLOSUM62 typed from memory that was NOT compared with NCBI's file).
+ *
+ * fd_seq_greedy(..): length-ordered greedy clustering (CD-HIT; MMseqs2 cluster-mode 2) on a relation matrix where it lies.
+ * rel [C,ld] uint8, ld >= C: i and j are related iff rel[min(i,j)][max(i,j)] != 0 -- only the strict upper triangle is read.
+ * order [C] int32 is the walk order.  Walk it: a chain that is still unlabelled founds a cluster, becomes its representative
+ * and takes every still-unlabelled chain related to it.  Then the clusters are numbered 0 .. K-1 by ascending smallest member:
+ * labels [C] int32 = the cluster of each chain (-1 for a chain that order does not name; entries of order outside [0, C) are
+ * passed over), rep [C] int32 = the founder of cluster k, -1 for k >= K; out [4] int32 = C, K, the size of the largest
+ * cluster, 0.  ws [2 C] int32 is working memory.  One block; a founder's round is a row scan by all threads between two
+ * barriers; the numbering is an ordered count: no atomics, two runs give the same words.  C == 0 returns FD_OK without a launch.
+ * Refused before any launch: C < 0 or above FD_SEQ_GREEDY_MAX_C, ld < C, a null or misaligned operand, ws, labels and rep not
+ * distinct. */
+#define FD_SEQ_MAX_L 2048
+#define FD_SEQ_LETTERS 21
+#define FD_SEQ_SLOTS 8
+#define FD_SEQ_MAX_SCORE 127
+#define FD_SEQ_MAX_GAP 1023
+#define FD_SEQ_GREEDY_MAX_C (1 << 30)
+int fd_seq_align(const unsigned char* letters, const long* offsets, int C, const int* ids_a, int Pa, const int* ids_b, int Pb,
+                 const int* subst, int gap_open, int gap_extend, int upper_only, int* out, void* stream);
+int fd_seq_greedy(const unsigned char* rel, long ld, int C, const int* order, int* ws, int* labels, int* rep, int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

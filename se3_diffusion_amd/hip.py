@@ -309,6 +309,8 @@ _SIGS = {
     "fd_cif_read_summary": "plpi" + "i" + "ppp" + "s",
     "fd_cif_read_count": "plpi" + "ii" + "ppp" + "s",
     "fd_cif_read_fill": "plpi" + "ii" + "ppp" + "ll" + "pppppp" + "pppp" + "s",
+    "fd_seq_align": "ppi" + "pipi" + "p" + "iii" + "p" + "s",
+    "fd_seq_greedy": "pli" + "p" + "pppp" + "s",
 }
 # exact argument lists, kept next to the header for the symbol-export test
 _CT = {"p": c_void_p, "i": c_int, "l": c_long, "f": c_float, "d": c_double, "S": c_void_p, "s": c_void_p}

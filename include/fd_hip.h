@@ -1442,6 +1442,51 @@ int fd_cif_read_fill(const unsigned char* text, long n, const long* file_offsets
                      float* b_factors, long* aatype, long* residue_index, int* row_dropped, long* chain_first, int* chain_file,
                      int* chain_model, int* chain_id, void* stream);
 
+/* ---- inflating gzip members (se3_diffusion_amd/csrc/fd_inflate.hip) ----
+ * The text that the two sections above read, from files that may be gzip-compressed.  F input files lie end to end in in [n_in]
+ * uint8, file f being the bytes in_offsets[f] .. in_offsets[f+1] (int64 [F+1]); its text goes to out [n_out] uint8 at
+ * out_offsets[f] .. out_offsets[f+1] (int64 [F+1]).  kind [F] int32: 0, a plain file, is copied through (its two sizes are equal);
+ * anything else, a gzip file, is inflated, and the caller has sized its place from the ISIZE word, the file's last four bytes.
+ * One launch, one wave per file; out is the window, there is no other buffer.  Nothing outside a file's own two ranges is read
+ * or written, whatever the file holds, and the work is bounded by the file's length: a corrupt file ends in a status.
+ *
+ * A GZIP FILE is ONE member (RFC 1952): the bytes 1f 8b; CM = 8; FLG, whose bits 5 .. 7 are clear; MTIME, XFL and OS, not looked
+ * at; with FEXTRA two bytes XLEN and that many bytes, with FNAME and with FCOMMENT the bytes up to a zero byte, with FHCRC two
+ * bytes -- all skipped, the header CRC is NOT checked; a raw DEFLATE stream (RFC 1951); CRC32 and ISIZE, four bytes each, the
+ * lowest first.  The DEFLATE stream has stored, fixed-Huffman and dynamic-Huffman blocks, lengths 3 .. 258 and distances
+ * 1 .. 32768 that may reach back to the file's first output byte and no further.
+ * status [F] int64 = 0, or 16 (a byte position in the input file) + kind; where a file ends early the position is its length:
+ *   FD_INFLATE_HEADER    not a gzip header: other magic bytes, CM != 8, a reserved FLG bit
+ *   FD_INFLATE_ENDS      the file ends before the member is complete (header, stream or trailer); also offsets that leave in or out
+ *   FD_INFLATE_BLOCK     block type 3, or a stored block whose LEN is not ~NLEN
+ *   FD_INFLATE_CODES     a dynamic block's code lengths: more than 286 literal/length or 30 distance codes, a repeat with nothing
+ *                        to repeat or past the end, a set that is over-subscribed, or incomplete -- except, as zlib has it, a
+ *                        literal/length or distance set with no code at all or with a single code of one bit -- or no code for
+ *                        the end of the block
+ *   FD_INFLATE_SYMBOL    a code that the set does not hold, length symbol 286 or 287, distance symbol 30 or 31, or a distance
+ *                        that reaches in front of the file's first output byte
+ *   FD_INFLATE_SIZE      the stream gives more or fewer bytes than the file's place holds, or ISIZE is not that size mod 2^32;
+ *                        a plain file whose two sizes differ
+ *   FD_INFLATE_CRC       with verify != 0: the CRC32 of the output is not the trailer's (taken by the same wave, a slice per
+ *                        lane, the slices joined by x^(8 bytes) mod the polynomial)
+ *   FD_INFLATE_TRAILING  bytes behind the trailer: a second member, BGZF blocks, padding.  They are named, never silently cut.
+ * The first of these that the member meets in the order of its bytes is reported; TRAILING, SIZE, CRC in that order at the
+ * trailer.  (Bytes behind the trailer also make the file's last four bytes something other than ISIZE: where the place sized
+ * from them is too small, SIZE is met first, inside the stream.)  The output of a file with a nonzero status is unspecified
+ * within its place.
+ * Not read: several members in one file, BGZF, the zlib (RFC 1950) and raw-deflate wrappers, other compressors.
+ * F == 0 returns FD_OK without a launch.  Refused before any launch: a negative size, a null or misaligned operand. */
+#define FD_INFLATE_HEADER 1
+#define FD_INFLATE_ENDS 2
+#define FD_INFLATE_BLOCK 3
+#define FD_INFLATE_CODES 4
+#define FD_INFLATE_SYMBOL 5
+#define FD_INFLATE_SIZE 6
+#define FD_INFLATE_CRC 7
+#define FD_INFLATE_TRAILING 8
+int fd_inflate(const unsigned char* in, long n_in, const long* in_offsets, int F, const int* kind, unsigned char* out, long n_out,
+               const long* out_offsets, int verify, long* status, void* stream);
+
 /* ---- sequence alignment and clustering (se3_diffusion_amd/csrc/fd_seq.hip) ----
  * Sequences are packed as the chain store packs chains: letters [T] uint8, values 0 .. 20 in the reference's restypes order
  * (ARNDCQEGHILKMFPSTWYV, 20 = X), chain c being the rows offsets[c] .. offsets[c+1] - 1 (offsets [C+1] int64, 0 first, not

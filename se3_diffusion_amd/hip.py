@@ -309,6 +309,7 @@ _SIGS = {
     "fd_cif_read_summary": "plpi" + "i" + "ppp" + "s",
     "fd_cif_read_count": "plpi" + "ii" + "ppp" + "s",
     "fd_cif_read_fill": "plpi" + "ii" + "ppp" + "ll" + "pppppp" + "pppp" + "s",
+    "fd_inflate": "plpip" + "plp" + "ip" + "s",
     "fd_seq_align": "ppi" + "pipi" + "p" + "iii" + "p" + "s",
     "fd_seq_greedy": "pli" + "p" + "pppp" + "s",
 }

@@ -28,7 +28,8 @@ columns, residues numbered by an ordered scan and atoms placed, on the device.
 
 Reading back what format_pdb wrote gives float32(rint(x 1000) / 1000).  Not read: SEQRES and the other header records; of
 alternate locations the first is kept, not the one of the highest occupancy (parse_pdb's note).  mmCIF is read by parse_mmcif
-(csrc/fd_cif_read.hip): the _atom_site loop under the same rules, nothing else of the file.
+(csrc/fd_cif_read.hip): the _atom_site loop under the same rules, nothing else of the file.  Both readers take gzip files
+(NNNN.cif.gz, pdbNNNN.ent.gz): inflate() (csrc/fd_inflate.hip) inflates one member per file on the device, a wave per file.
 """
 from __future__ import annotations
 
@@ -305,8 +306,8 @@ def _pack_chain(chain_id):
     return int.from_bytes(raw.ljust(4, b"\0"), "little", signed=True)
 
 
-def _gather_text(inputs, lib):
-    """(text uint8 on the device, 16-byte aligned; host int64 offsets [F+1]; names): host pieces are joined and uploaded in one copy"""
+def _pieces(inputs):
+    """(the entries as uint8 tensors and numpy arrays, their names)"""
     items = inputs if isinstance(inputs, (list, tuple)) else [inputs]
     pieces, names = [], []
     for k, it in enumerate(items):
@@ -323,6 +324,16 @@ def _gather_text(inputs, lib):
             names.append(os.fspath(it))
         else:
             raise TypeError(f"input {k}: expected bytes, a uint8 tensor or a path, got {type(it).__name__}")
+    return pieces, names
+
+
+def _gather_text(inputs, lib):
+    """(text uint8 on the device, 16-byte aligned; host int64 offsets [F+1]; names): host pieces are joined and uploaded in one copy"""
+    return _join(*_pieces(inputs), lib)
+
+
+def _join(pieces, names, lib):
+    """_gather_text's result for _pieces' entries"""
     offsets = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in pieces])]).astype(np.int64)
     on_dev = [p for p in pieces if isinstance(p, torch.Tensor) and (p.is_cuda or not lib.is_device)]
     dev = on_dev[0].device if on_dev else _device_of(None, lib)
@@ -347,6 +358,100 @@ def _gather_text(inputs, lib):
     return text, offsets, names
 
 
+INFLATE_KINDS = {1: "not a gzip header (magic bytes 1f 8b, CM = 8, no reserved flag)",
+                 2: "the file ends before the gzip member is complete",
+                 3: "block type 3, or a stored block whose LEN is not ~NLEN",
+                 4: "a code-length set that is over-subscribed or incomplete",
+                 5: "an invalid symbol, or a distance that reaches in front of the file's first byte",
+                 6: "more or fewer bytes than ISIZE says",
+                 7: "a CRC32 that is not the trailer's",
+                 8: "bytes behind the trailer (several members and BGZF are not read)"}     # FD_INFLATE_*
+_GZIP_MIN = 18                              # a header of 10 bytes and a trailer of 8
+
+
+def inflate(inputs, gzip="auto", verify=True, max_inflated=1 << 30):
+    """The texts of the input files laid end to end on the device, gzip members inflated there (csrc/fd_inflate.hip; include/fd_hip.h
+    is the specification).  inputs: what parse_pdb takes -- bytes, a uint8 tensor, a path, or a list of these, each entry one
+    file.  Returns (text, offsets, names): text uint8 on the device, 16-byte aligned; offsets a host int64 [F+1] array; the names.
+
+    gzip="auto": a host entry or a path whose first two bytes are 1f 8b is a gzip file (no PDB or mmCIF text begins with 0x1f);
+    a tensor that is already on the device is taken as text.  gzip=True: every entry is a gzip file; the ISIZE words of entries
+    on the device are gathered there and cost one read-back.  gzip=False: nothing is inflated.  A call in which no entry is a
+    gzip file does what it did before there was this function: no launch, no read-back.
+
+    ISIZE (the last four bytes) sizes each file's place, the output is allocated once, compressed and plain host pieces go up in
+    one copy, and ONE launch (a wave per file) inflates the gzip files and copies the plain ones through.  verify: the same
+    launch checks each member's CRC32.  One read-back, the status.  ValueError: an entry declared gzip of fewer than 18 bytes, an
+    ISIZE above max_inflated (bytes), or a file the device refuses (INFLATE_KINDS) -- the message names the file's index and
+    name, the byte position in the file and the kind; the smallest index wins.
+
+    Read: one gzip member per file (RFC 1952: FEXTRA, FNAME, FCOMMENT and FHCRC skipped, the header CRC not checked) around a
+    DEFLATE stream (RFC 1951) of stored, fixed and dynamic blocks.  Not read, and refused by name, not silently cut: several
+    members in one file and BGZF.  Not read at all: the zlib and raw-deflate wrappers, other compressors.  A file is inflated by
+    one wave, so a single large file goes at one wave's rate, about 5 MB/s of text: 2,000 N=256 files take 26 ms, one 25 MB file
+    5 s (profiles/inflate_cost.txt).  Inflate a handful of files or one large file on the host."""
+    if not (gzip == "auto" or gzip is True or gzip is False):
+        raise ValueError(f"gzip={gzip!r}: expected 'auto', True or False")
+    lib = hip.get_lib()
+    pieces, names = _pieces(inputs)
+    on_dev = [isinstance(p, torch.Tensor) and (p.is_cuda or not lib.is_device) for p in pieces]
+    host = lambda p, sl: bytes(p[sl].numpy()) if isinstance(p, torch.Tensor) else p[sl].tobytes()
+    if gzip == "auto":
+        gz = [not d and p.shape[0] >= 2 and host(p, slice(0, 2)) == b"\x1f\x8b" for p, d in zip(pieces, on_dev)]
+    else:
+        gz = [bool(gzip)] * len(pieces)
+    if not any(gz):
+        return _join(pieces, names, lib)
+    F = len(pieces)
+    for f in range(F):
+        if gz[f] and pieces[f].shape[0] < _GZIP_MIN:
+            raise ValueError(f"cannot be inflated: file {f} ({names[f]}) has {int(pieces[f].shape[0])} bytes, a gzip member has at "
+                             f"least {_GZIP_MIN}")
+    data, in_off, _ = _join(pieces, names, lib)
+    dev = data.device
+    sizes = np.diff(in_off)
+    for f in range(F):
+        if gz[f] and not on_dev[f]:
+            sizes[f] = int.from_bytes(host(pieces[f], slice(-4, None)), "little")
+    far = [f for f in range(F) if gz[f] and on_dev[f]]
+    if far:
+        at = torch.from_numpy((in_off[np.asarray(far) + 1, None] - 4 + np.arange(4)[None]).reshape(-1)).to(dev)
+        words = data[at].cpu().numpy().reshape(-1, 4).astype(np.int64)
+        sizes[far] = words[:, 0] | words[:, 1] << 8 | words[:, 2] << 16 | words[:, 3] << 24
+    for f in range(F):
+        # (DEFLATE gives at most 1032 bytes for one, 258 for two bits: an ISIZE above that is not the stream's, the file is cut or
+        # damaged, and the device says where -- in a place no larger than the stream could fill)
+        most = 1032 * int(in_off[f + 1] - in_off[f])
+        if gz[f] and sizes[f] > max_inflated and sizes[f] <= most:
+            raise ValueError(f"cannot be inflated: file {f} ({names[f]}) gives its inflated size (ISIZE) as {int(sizes[f])} bytes, "
+                             f"above max_inflated={max_inflated}")
+        if gz[f]:
+            sizes[f] = min(sizes[f], most, max(max_inflated, 0))
+    out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    kinds = np.zeros(F + (F & 1), np.int32)
+    kinds[:F] = gz
+    meta = torch.from_numpy(np.concatenate([in_off, out_off, kinds.view(np.int64)])).to(dev)      # one upload
+    text = torch.empty(int(out_off[-1]), dtype=torch.uint8, device=dev)
+    if text.data_ptr() % 16:
+        text = torch.empty(int(out_off[-1]) + 16, dtype=torch.uint8, device=dev)
+        text = text[(-text.data_ptr()) % 16:][:int(out_off[-1])]
+    status = torch.empty(F, dtype=torch.int64, device=dev)
+    lib.call("fd_inflate", data, int(data.numel()), meta[:F + 1], F, meta[2 * F + 2:].view(torch.int32), text, int(text.numel()),
+             meta[F + 1:2 * F + 2], int(bool(verify)), status)
+    words = status.cpu().numpy()
+    bad = np.flatnonzero(words)
+    if len(bad):
+        f = int(bad[0])
+        pos, kind = divmod(int(words[f]), 16)
+        raise ValueError(f"cannot be inflated: {INFLATE_KINDS.get(kind, kind)} in file {f} ({names[f]}), byte {pos} (kind {kind})")
+    return text, out_off, names
+
+
+def _text_of(inputs, gzip, lib):
+    """_gather_text's result for the readers: through inflate unless gzip=False"""
+    return _gather_text(inputs, lib) if gzip is False else inflate(inputs, gzip=gzip)
+
+
 def _empty_parsed(dev, F, T, C):
     """a ParsedPdb of T rows in C segments from F files for a fill kernel to write into: zeros where no record may write"""
     i64 = dict(dtype=torch.int64, device=dev)
@@ -365,7 +470,7 @@ def _close(out, dropped):
     out.n_dropped.index_add_(0, out.chain_file[seg].to(torch.int64), dropped.to(torch.int64))
 
 
-def parse_pdb(text_or_paths, hetatm=False, model="first"):
+def parse_pdb(text_or_paths, hetatm=False, model="first", gzip="auto"):
     """Read PDB files into atom37 arrays on the device (csrc/fd_pdb_read.hip; include/fd_hip.h is the specification).
 
     text_or_paths: bytes, a uint8 tensor already on the device (format_pdb's result), a path, or a list of these -- each entry is
@@ -380,11 +485,16 @@ def parse_pdb(text_or_paths, hetatm=False, model="first"):
     Three differences from Biopython's object model, which the reference reads through: HETATM records (above); of several records
     for one atom of a residue (alternate locations, duplicates) the FIRST is kept and the others counted in n_dropped, where
     Biopython keeps the alternate location of the highest occupancy; a chain ID that comes back after another chain begins a
-    new segment, where Biopython merges the two.  SEQRES and the other header records are not read; mmCIF is parse_mmcif's."""
+    new segment, where Biopython merges the two.  SEQRES and the other header records are not read; mmCIF is parse_mmcif's.
+
+    gzip="auto": a host entry or a path that begins with the bytes 1f 8b (NNNN.ent.gz) is inflated on the device first, in one
+    launch for all files (inflate(), which also says what gzip=True and False mean and what is refused): ONE more launch and one
+    more read-back of its own, the status -- it is not folded into the read-back above.  A call without a gzip entry takes the
+    path it took before there was gzip=: the same launches, the same single read-back."""
     if model not in ("first", "all"):
         raise ValueError(f"model={model!r}: expected 'first' or 'all'")
     lib = hip.get_lib()
-    text, offsets, names = _gather_text(text_or_paths, lib)
+    text, offsets, names = _text_of(text_or_paths, gzip, lib)
     dev, n, F = text.device, int(text.numel()), len(offsets) - 1
     i64 = dict(dtype=torch.int64, device=dev)
     empty = lambda T, C: _empty_parsed(dev, F, T, C)
@@ -431,7 +541,7 @@ CIF_KINDS = {1: "a row with a wrong number of tokens, an unclosed quote or more 
              7: "a model number that is not an integer"}
 
 
-def parse_mmcif(text_or_paths, hetatm=False, model="first", ids="auth"):
+def parse_mmcif(text_or_paths, hetatm=False, model="first", ids="auth", gzip="auto"):
     """Read the _atom_site loop of mmCIF files into atom37 arrays on the device (csrc/fd_cif_read.hip; include/fd_hip.h is the
     specification).  The inputs, the result and the rules for residues, segments, slots and models are parse_pdb's, with the
     pdbx_PDB_model_num column in place of ENDMDL records: model="first" keeps the rows that carry the model number of the file's
@@ -448,8 +558,8 @@ def parse_mmcif(text_or_paths, hetatm=False, model="first", ids="auth"):
     atom_site loop, or with atom_site in key-value form, gives no row.
 
     Not read: _entity_poly_seq and any SEQRES-like alignment; the header items the reference's metadata uses (resolution,
-    method, oligomeric state); rows that span lines and text fields inside the loop; several tags on one line; gzip (pass the
-    inflated bytes).  parse_pdb's three differences from Biopython's object model hold here too.  The reader is checked against
+    method, oligomeric state); rows that span lines and text fields inside the loop; several tags on one line.  gzip files are
+    inflated on the device first, as parse_pdb's are (gzip=, pdb.inflate).  parse_pdb's three differences from Biopython's object model hold here too.  The reader is checked against
     parse_pdb on the same structures and against a pure-Python tokeniser written from the header's rules (tests/test_mmcif_read.py),
     NOT against Biopython's MMCIFParser, which does not exist where this project is built."""
     if model not in ("first", "all"):
@@ -457,7 +567,7 @@ def parse_mmcif(text_or_paths, hetatm=False, model="first", ids="auth"):
     if ids not in ("auth", "label"):
         raise ValueError(f"ids={ids!r}: expected 'auth' or 'label'")
     lib = hip.get_lib()
-    text, offsets, names = _gather_text(text_or_paths, lib)
+    text, offsets, names = _text_of(text_or_paths, gzip, lib)
     dev, n, F = text.device, int(text.numel()), len(offsets) - 1
     i64 = dict(dtype=torch.int64, device=dev)
     if n == 0:
